@@ -13,11 +13,19 @@ rank owns 65536 trajectories of one deterministic stream; `--scaling strong` div
 65536-trajectory batch over the ranks instead).
 
 One JSON line on rank 0; `roofline` prices the dominant kernel against the 8 TB/s HBM peak by
-ALGORITHMIC bytes (3608 B/solve at S=16,o=4,f64 -- SURVEY.md §8d); `cpu_baseline` times the CPU
-oracle (a restatement of the reference's dense path, kind "port") on a bounded sample.
+ALGORITHMIC bytes (3608 B/solve at S=16,o=4,f64 -- SURVEY.md §8d).  A plain run does only that:
+set up, warm up, time --steps steps, write the outputs (--dump-outputs DIR), print the line.
 
-Side records on the same line (N=1 only; `--no-side-records` skips them), each timed the same way
-(HIP events on the launch stream, inputs resident in HBM):
+`--dump-outputs DIR` writes what the last timed step computed, as the caller receives it: DIR/coeffs.npy
+(float64, [n][S][3][2o], trajectory-major whatever --segment-major says) and DIR/coeffs_index.npy (float64,
+the n trajectory indices into rank 0's batch).  The whole batch while it fits in 48 MB, above that a fixed,
+seeded sample of trajectories, so two builds run with the same arguments can be compared output for output.
+
+`--full` adds everything else to the same line (N=1 only): `cpu_baseline` times the CPU oracle (a
+restatement of the reference's dense path, kind "port") on a bounded sample, with the parity figures and
+the structured CPU solver beside it (`--no-cpu-baseline` skips them), and the side records below
+(`--no-side-records` skips them), each timed the same way (HIP events on the launch stream, inputs
+resident in HBM):
   streaming     B=524288 (BASELINE C4's whole batch on one GPU: 1.9 GB per step, 7x the Infinity Cache)
   c2            BASELINE C2 (B=4096, S=8): the small-batch launch
   yaml_default  the reference's shipped configuration (minimum_snap_config.yaml:5-10: order 2,
@@ -102,6 +110,24 @@ def timed(step, steps, warmup, dev):
     e1.record()
     torch.cuda.synchronize(dev)
     return e0.elapsed_time(e1) / steps
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs: whole batch up to this size, a seeded sample of trajectories above it
+DUMP_SEED = 20260501
+
+
+def dump_outputs(dirname, out, B, S, o, segment_major):
+    """--dump-outputs: the coefficients the last timed step wrote, in the caller's trajectory-major layout, as float64,
+    with the trajectory indices they belong to (float64 too; exact below 2^53)."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    n = min(B, DUMP_BYTES // (S * 3 * 2 * o * 8))
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=n, replace=False))
+    co = out.view(S, B, 3, 2 * o).permute(1, 0, 2, 3) if segment_major else out
+    if n < B:
+        co = co[torch.from_numpy(idx).to(co.device)]
+    np.save(os.path.join(dirname, "coeffs.npy"), co.contiguous().cpu().numpy().astype(np.float64))
+    np.save(os.path.join(dirname, "coeffs_index.npy"), idx.astype(np.float64))
 
 
 def bench_uniform(csp, dev, B, S, o, steps, warmup, config_id, pw=0.0, vw=0.0, label=""):
@@ -335,9 +361,13 @@ def main():
     ap.add_argument("--order", type=int, default=4)
     ap.add_argument("--path-weight", type=float, default=0.0, help="side benchmark: path-deviation penalty on (row A7)")
     ap.add_argument("--vel-zero-weight", type=float, default=0.0)
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU baseline work")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-records", action="store_true", help="only the headline workload (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, parity figures and side records (off: only the headline workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the coefficients of the last timed step as DIR/*.npy (headline workload only)")
+    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU baseline work (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-side-records", action="store_true", help="--full without the side records")
     ap.add_argument("--force-generic", action="store_true")
     ap.add_argument("--segment-major", action="store_true",
                     help="experiment: CSP_FLAG_SEGMENT_MAJOR coefficient layout [S][B][3][2o]")
@@ -354,6 +384,8 @@ def main():
     ap.add_argument("--host-path", action="store_true",
                     help="also time the CSP_MEM_HOST boundary (PCIe-inclusive; reported as a side note, never `value`)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload == "c5":
+        ap.error("--dump-outputs writes the headline workload's outputs, not --workload c5's")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -424,6 +456,8 @@ def main():
         t = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device="cpu" if share else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kernel_ms = float(t[0]), float(t[1])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, B, S, o, args.segment_major)
 
     e2e = end_to_end(args, csp, dev, dist if use_dist else None, rank, world, share) if args.end_to_end else None
 
@@ -481,7 +515,7 @@ def main():
             for _ in range(reps):
                 csp.solve_batch(wp, tm, order=o, force_generic=args.force_generic, out=h_out)
             res["host_path_solves_per_s"] = B * reps / (time.perf_counter() - t1)
-        if world == 1 and not args.no_side_records:
+        if args.full and world == 1 and not args.no_side_records:
             side_steps = max(5, min(args.steps, 20))
             try:
                 res["streaming"], p_, _, _ = bench_uniform(csp, dev, 524288, 16, 4, side_steps, 3, 4,
@@ -502,7 +536,7 @@ def main():
                 res["c5"] = bench_c5(csp, dev, 65536, side_steps, 3)
             except Exception as e:   # a side record never takes the headline down
                 res["side_record_error"] = repr(e)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb, ref, n = cpu_baseline(o, S, wp, tm, args.cpu_budget, args.path_weight, args.vel_zero_weight)
             res["cpu_baseline"] = cb
             # SURVEY.md 8(d) also asks for the one-core figure: a short sample of the same batch

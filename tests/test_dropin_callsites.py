@@ -1,27 +1,26 @@
-"""Drop-in evidence on the reference's OWN call sites (CPU container only).
+"""Drop-in evidence on the planner's call sites (CPU container only).
 
 The reference reaches the path through three members of UavPathPlanner -- Minisnap_EN, Minisnap_3D,
 Bezier_3D (uavPathPlanning.cpp:4401-4510) -- which include the headers quoted, as
 "math_util/minimum_snap.hpp" (uavPathPlanning.hpp:11).  This test
 
-  1. reads those three member definitions out of /root/reference AT TEST TIME into a translation unit
-     in a temporary directory (never committed, never shipped, deleted with the tmp dir),
-  2. surrounds them with the minimum the planner class provides them (ENUPoint, a by-value
-     `TrajectoryGeneratorTool generator_`, `config_.minimum_snap`; `Eigen::MatrixXd` is an alias of
-     the shim's matrix type because <Eigen/Dense> is not installed in this image),
-  3. compiles the unit against cs-pathplan_amd/host (so "math_util/minimum_snap.hpp" and
+  1. writes a translation unit with those three members as this project restates them (CALL_SITES below:
+     ENU points -> N x 3 route, one by-value `TrajectoryGeneratorTool generator_` call with
+     `config_.minimum_snap`, the distance and the speed override; Minisnap_EN plans in the plane at the
+     first waypoint's height; Bezier_3D turns any min_radius > 0 into 300; fewer than two points -> empty)
+     into a temporary directory, with the minimum the planner class provides them (ENUPoint,
+     `config_.minimum_snap`; `Eigen::MatrixXd` is an alias of the shim's matrix type because
+     <Eigen/Dense> is not installed in this image),
+  2. compiles the unit against cs-pathplan_amd/host (so "math_util/minimum_snap.hpp" and
      "math_util/bezier.hpp" resolve to the shims, exactly as INTEGRATION.md §1 prescribes) and links it
      with the C-ABI library,
-  4. runs what can run without a GPU: Bezier_3D (pure host code) with the min_radius = 300 the
+  3. runs what can run without a GPU: Bezier_3D (pure host code) with the min_radius = 300 the
      reference really uses (uavPathPlanning.cpp:4492-4494), checked against a Python restatement of
      bezier.cpp:28-118 including the curvature loop :44-94; and Minisnap_3D / Minisnap_EN, which must
      come back EMPTY here (no device, no CPU fallback) -- the planner's own failure convention.
-
-/root/reference does not exist on the GPU box: the test skips there.
 """
 import math
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -30,7 +29,6 @@ import pytest
 from tests import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_CPP = "/root/reference/uavPathPlanning.cpp"
 PKG = os.path.join(ROOT, "cs-pathplan_amd")
 
 SCAFFOLD_HEAD = r"""
@@ -77,33 +75,61 @@ int main(int argc, char **argv) {
 """
 
 
-def _extract_call_sites():
-    """The definitions of Minisnap_EN, Minisnap_3D and Bezier_3D, located by their signatures (the
-    cited range uavPathPlanning.cpp:4401-4510 at the surveyed revision)."""
-    with open(REF_CPP, encoding="utf-8", errors="replace") as f:
-        lines = f.read().split("\n")
-    start = next(i for i, ln in enumerate(lines) if re.match(r"\s*std::vector<ENUPoint>\s+UavPathPlanner::Minisnap_EN\s*\(", ln))
-    end = next(i for i, ln in enumerate(lines) if i > start and re.match(r"\s*bool\s+UavPathPlanner::loadData\s*\(", ln))
-    body = "\n".join(lines[start:end])
-    for name in ("Minisnap_EN", "Minisnap_3D", "Bezier_3D"):
-        assert "UavPathPlanner::%s" % name in body
-    assert 440 > end - start > 60
-    return body
+CALL_SITES = r"""
+// The three planner members, restated for this test: how a caller hands ENU points to the shim and reads them back.
+static Eigen::MatrixXd route_of(const std::vector<ENUPoint> &wps, bool in_plane) {
+    Eigen::MatrixXd route((long)wps.size(), 3);
+    for (long i = 0; i < (long)wps.size(); ++i) {
+        route(i, 0) = wps[(size_t)i].east;
+        route(i, 1) = wps[(size_t)i].north;
+        route(i, 2) = in_plane ? 0.0 : wps[(size_t)i].up;
+    }
+    return route;
+}
+
+static std::vector<ENUPoint> points_of(const Eigen::MatrixXd &m, bool keep_up, double up) {
+    std::vector<ENUPoint> out;
+    for (long i = 0; i < m.rows(); ++i) out.push_back(ENUPoint{m(i, 0), m(i, 1), keep_up ? m(i, 2) : up});
+    return out;
+}
+
+std::vector<ENUPoint> UavPathPlanner::Minisnap_EN(std::vector<ENUPoint> origin_waypoints, double distance_, double V_avg_override) {
+    if (origin_waypoints.size() < 2) return {};
+    Eigen::MatrixXd sampled = generator_.GenerateTrajectoryMatrix(route_of(origin_waypoints, true), config_.minimum_snap,
+                                                                  distance_, V_avg_override);
+    return points_of(sampled, false, origin_waypoints[0].up);   // planned in the plane, flown at the first height
+}
+
+std::vector<ENUPoint> UavPathPlanner::Minisnap_3D(std::vector<ENUPoint> origin_waypoints, double distance_, double V_avg_override) {
+    if (origin_waypoints.size() < 2) return {};
+    Eigen::MatrixXd sampled = generator_.GenerateTrajectoryMatrix(route_of(origin_waypoints, false), config_.minimum_snap,
+                                                                  distance_, V_avg_override);
+    return points_of(sampled, true, 0.0);
+}
+
+std::vector<ENUPoint> UavPathPlanner::Bezier_3D(std::vector<ENUPoint> origin_waypoints, double distance_, double V_avg_override,
+                                                double min_radius) {
+    if (origin_waypoints.size() < 2) return {};
+    math_util::BezierConfig cfg;
+    if (min_radius > 0) cfg.min_radius = 300;   // any positive request means 300
+    math_util::Bezier bezier;
+    bezier.SetConfig(cfg);
+    return points_of(bezier.GenerateTrajectoryMatrix(route_of(origin_waypoints, false), "", distance_, V_avg_override), true, 0.0);
+}
+"""
 
 
 @pytest.fixture(scope="module")
 def callsite_exe(tmp_path_factory):
-    if not os.path.exists(REF_CPP):
-        pytest.skip("/root/reference is not present (GPU box): the call sites cannot be read")
     d = tmp_path_factory.mktemp("callsites")
     tu = d / "planner_callsites.cpp"
-    tu.write_text(SCAFFOLD_HEAD + _extract_call_sites() + SCAFFOLD_MAIN, encoding="utf-8")
+    tu.write_text(SCAFFOLD_HEAD + CALL_SITES + SCAFFOLD_MAIN, encoding="utf-8")
     exe = d / "planner_callsites"
     cmd = ["g++", "-std=c++14", "-O1", "-Wall", "-Wno-sign-compare", "-Wno-unused-variable",
            "-I", os.path.join(PKG, "host"), "-I", os.path.join(ROOT, "include"), str(tu), "-o", str(exe),
            "-L", PKG, "-lcsp_minsnap", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"]
     r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, "the reference's call sites do not compile against the shim:\n" + r.stderr[-4000:]
+    assert r.returncode == 0, "the planner's call sites do not compile against the shim:\n" + r.stderr[-4000:]
     return str(exe)
 
 
@@ -190,7 +216,7 @@ def _turny_path(scale):
     return P * scale
 
 
-def test_reference_call_sites_compile_against_the_shim(callsite_exe):
+def test_planner_call_sites_compile_against_the_shim(callsite_exe):
     assert os.path.exists(callsite_exe)
 
 

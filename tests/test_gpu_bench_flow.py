@@ -38,7 +38,7 @@ def _run(cmd, env=None):
 
 
 def test_bench_json_contract_single_gpu():
-    d = _run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--batch", "8192", "--cpu-budget", "1"])
+    d = _run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "2", "--batch", "8192", "--cpu-budget", "1"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -47,6 +47,24 @@ def test_bench_json_contract_single_gpu():
     assert abs(d["roofline"]["frac"] - d["roofline"]["achieved"] / 8000.0) < 1e-12
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] >= 1
     assert d["parity_per_power_rel_err"] < 5e-8 and d["parity_max_rel_err"] < 1e-8   # the gate is the per-power figure
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(csp, tmp_path):
+    """A plain run (no --full) prints the headline line only, times exactly --steps steps, and --dump-outputs writes the
+    coefficients of the timed path: the whole 8192-trajectory batch, bit-equal with one solve_batch call on the same inputs."""
+    import torch
+    d = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "8192",
+              "--dump-outputs", str(tmp_path)])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "solves/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    for k in ("cpu_baseline", "parity_per_power_rel_err", "streaming", "c2", "c5", "single_flight"):
+        assert k not in d, k
+    co, idx = np.load(tmp_path / "coeffs.npy"), np.load(tmp_path / "coeffs_index.npy")
+    assert co.dtype == np.float64 and np.array_equal(idx, np.arange(8192))
+    wp, tm = synth.make_batch(8192, 16, config_id=3)
+    ref = csp.solve_batch(torch.from_numpy(wp).cuda(), torch.from_numpy(tm).cuda(), order=4).coeffs
+    torch.cuda.synchronize()
+    assert np.array_equal(co, ref.cpu().numpy())
 
 
 def test_bench_two_ranks_share_one_gpu():
