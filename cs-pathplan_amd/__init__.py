@@ -416,13 +416,15 @@ class PreparedMixed:
 
 
 def solve_mixed(orders, waypoints, times, seg_offsets, bc=None, vel_zero_weight=0.0, vel_zero_weight_per_traj=None,
-                max_segments=None, want_status=False, stream=None):
+                max_segments=None, want_status=False, stream=None, out=None):
     """csp_minsnap_solve_mixed: a ragged batch whose trajectories carry their own derivative order (2..5).
-    numpy inputs -> CSP_MEM_HOST, torch CUDA tensors -> CSP_MEM_DEVICE.  Returns MixedResult."""
+    numpy inputs -> CSP_MEM_HOST, torch CUDA tensors -> CSP_MEM_DEVICE.  Returns MixedResult.  `out` (host form only): the
+    flat coefficient array to write, of at least mixed_coeff_total() elements; the blocks of skipped trajectories keep
+    their contents."""
     if _is_torch(waypoints):
         import torch
-        if vel_zero_weight_per_traj is not None:
-            raise ValueError("per-trajectory weights: use the host-memory form or PreparedMixed")
+        if vel_zero_weight_per_traj is not None or out is not None:
+            raise ValueError("per-trajectory weights or a given output: use the host-memory form or PreparedMixed")
         p = PreparedMixed(orders, waypoints, times, seg_offsets, bc, vel_zero_weight, max_segments, want_status=want_status, stream=stream)
         p.run()
         return MixedResult(p.out, p.coeff_offsets, p.status)
@@ -437,7 +439,11 @@ def solve_mixed(orders, waypoints, times, seg_offsets, bc=None, vel_zero_weight=
     if max_segments is None:
         max_segments = int(np.max(np.diff(seg_offsets))) if B else 1
     bc = np.zeros((1, 4, 3), dtype=npdt) if bc is None else np.ascontiguousarray(bc, dtype=npdt).reshape(-1, 4, 3)
-    out = np.empty(max(mixed_coeff_total(orders, seg_offsets, dtype == DTYPE_F32), 1), dtype=npdt)
+    need = max(mixed_coeff_total(orders, seg_offsets, dtype == DTYPE_F32), 1)
+    if out is None:
+        out = np.empty(need, dtype=npdt)
+    elif not (isinstance(out, np.ndarray) and out.dtype == npdt and out.flags.c_contiguous and out.size >= need):
+        raise ValueError("out: a contiguous %s array of at least %d elements" % (np.dtype(npdt).name, need))
     cof = np.empty(B + 1, dtype=np.int64)
     stt = np.empty(B, dtype=np.int32) if want_status else None
     vwp = np.ascontiguousarray(vel_zero_weight_per_traj, dtype=np.float64) if vel_zero_weight_per_traj is not None else None

@@ -10,6 +10,8 @@
 
 #include <hip/hip_runtime.h>
 #include "minsnap_hoststage.h"
+#include "alt_cr_layout.h"
+#include <atomic>
 #include <cmath>
 
 namespace {
@@ -418,16 +420,16 @@ __device__ __forceinline__ CrStore cr_store(double *lds, double *ws_cr, int64_t 
     return CrStore{fits ? lds : ws_cr, N2};
 }
 
-// workspace of problem b for the cyclic-reduction kernels: 14 doubles per sample (13 per block row = 6.5 per sample, the
-// solution, the active flags)
+// workspace of problem b for the cyclic-reduction kernels: its region of alt_cr_layout.h (solution, block rows, active flags)
 __global__ void __launch_bounds__(kCrThreads) alt_optimize_cr_kernel(AltArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn_lds[];
     const int64_t b = blockIdx.x;
     const int64_t o = a.off[b], n = a.off[b + 1] - o;
     if (n <= 0) return;
     const double *xyz = a.xyz + o * 3, *elev = a.a + o;
-    double *ws = a.ws + o * 14, *out = a.out + o;
-    double *x = ws, *store = ws + 2 * ((n + 1) / 2) + 2;
+    double *out = a.out + o;
+    const csp::alt::CrRegion r = csp::alt::cr_region(o, b, n);
+    double *x = a.ws + r.x, *store = a.ws + r.store;
     const csp_alt_params p = a.p;
     cr_solve(cr_store(dyn_lds, store, n), xyz, n, p.lambda_smooth, p.max_climb_rate,
              [&](int64_t i) { return isnan(elev[i]) ? 0.0 : p.lambda_follow; },
@@ -450,10 +452,9 @@ __global__ void __launch_bounds__(kCrThreads) alt_global_smooth_cr_kernel(AltArg
     const int64_t o = a.off[b], n = a.off[b + 1] - o;
     if (n <= 0) { if (a.solves && threadIdx.x == 0) a.solves[b] = 0; return; }
     const double *xyz = a.xyz + o * 3, *zin = a.a + o;
-    double *ws = a.ws + o * 14, *out = a.out + o;
-    const int64_t N2 = (n + 1) / 2;
-    double *x = ws, *act = ws + 2 * N2 + 2 + 13 * N2;     // solution | block rows | active flags
-    double *store = ws + 2 * N2 + 2;
+    double *out = a.out + o;
+    const csp::alt::CrRegion r = csp::alt::cr_region(o, b, n);
+    double *x = a.ws + r.x, *store = a.ws + r.store, *act = a.ws + r.act;
     const csp_alt_params p = a.p;
     for (int64_t i = threadIdx.x; i < n; i += blockDim.x) act[i] = 0.0;
     __syncthreads();
@@ -483,16 +484,22 @@ __global__ void __launch_bounds__(kCrThreads) alt_global_smooth_cr_kernel(AltArg
 constexpr int64_t kWaveBatch = 2048;
 
 // a few LONG problems (the reference's own call: one): block cyclic reduction, one 1024-thread workgroup per problem
-constexpr int64_t kCrMaxBatch = 64, kCrMinAvgSamples = 512;
-inline bool use_cr(int64_t batch, int64_t total) { return batch <= kCrMaxBatch && total >= batch * kCrMinAvgSamples; }
+// (at most csp::alt::CR_MAX_BATCH problems: their workspace regions, alt_cr_layout.h, rely on it)
+constexpr int64_t kCrMinAvgSamples = 512;
+inline bool use_cr(int64_t batch, int64_t total) { return batch <= csp::alt::CR_MAX_BATCH && total >= batch * kCrMinAvgSamples; }
 
 template <typename KC>
 hipError_t launch_cr(KC cr_kernel, const AltArgs &a, hipStream_t st) {
-    static bool attr_done = false;   // > 64 KB of dynamic LDS needs the opt-in, once per kernel (this function is one per kernel)
-    if (!attr_done) {
+    // > 64 KB of dynamic LDS needs the opt-in, once per kernel (this function is one per kernel) and device: bit d of the mask
+    // for ordinal d (the attribute is set on the current device; two threads may both set it, which is harmless)
+    static std::atomic<uint64_t> attr_done{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
+    const uint64_t bit = dev < 64 ? 1ull << dev : 0;
+    if (!bit || !(attr_done.load(std::memory_order_acquire) & bit)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(cr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCrLdsBytes);
         if (e != hipSuccess) return e;
-        attr_done = true;
+        attr_done.fetch_or(bit, std::memory_order_release);
     }
     hipLaunchKernelGGL(cr_kernel, dim3((unsigned)a.B), dim3(kCrThreads), kCrLdsBytes, st, a);
     return hipGetLastError();
@@ -540,8 +547,9 @@ int run(K kernel, KW wave_kernel, KC cr_kernel, const double *a0, const double *
 }  // namespace
 
 // 4 doubles per sample for the recurrence kernels; the cyclic-reduction kernels (a few long problems) keep 13 doubles per
-// PAIR of samples, the solution and the active flags: 14 doubles per sample + slack covers both
-extern "C" size_t csp_alt_workspace_bytes(int64_t total_points) { return total_points > 0 ? (size_t)total_points * 14 * 8 + 4096 : 0; }
+// PAIR of samples, the solution and the active flags: 14 doubles per sample + slack (the per-problem pads) covers both
+// (alt_cr_layout.h)
+extern "C" size_t csp_alt_workspace_bytes(int64_t total_points) { return csp::alt::workspace_bytes(total_points); }
 
 extern "C" int csp_alt_optimize_heights_batch(const double *xyz, const double *elev, const int64_t *offsets, int64_t batch,
                                               const csp_alt_params *params, double *out_z, void *workspace,

@@ -272,9 +272,14 @@ struct RcclTransport {
                 CSP_HIP(hipEventCreateWithFlags(&d.in_ready[(size_t)c], hipEventDisableTiming));
                 CSP_HIP(hipEventCreateWithFlags(&d.solved[(size_t)c], hipEventDisableTiming));
             }
-            // the solve of a piece may need the generic kernel's workspace: sized for the largest piece
+            // the solve of a piece may need the generic kernel's workspace: sized for the largest piece (pieces are cut on
+            // 64-trajectory boundaries, so the last one can exceed n / nchunks)
             csp_minsnap_desc pd = *desc;
-            pd.batch = (n + nchunks - 1) / nchunks;
+            pd.batch = 0;
+            for (int c = 0; c < nchunks; ++c) {
+                const csp::shard::Piece p = csp::shard::piece_of(s.B, nd, nchunks, g, c);
+                if (p.hi - p.lo > pd.batch) pd.batch = p.hi - p.lo;
+            }
             Shape ps;
             if (validate(&pd, ps) != CSP_OK) return CSP_ERR_INVALID_ARG;
             d.ws_bytes = ws_bytes(&pd, ps, nullptr);
@@ -664,17 +669,22 @@ int csp_minsnap_solve_mixed(const csp_minsnap_desc *desc, const int32_t *orders,
     }
     // CSP_MEM_HOST: sizes from the caller's host arrays, staging through the cached arena, synchronous
     const int64_t total_seg = desc->seg_offsets[B];
+    // a trajectory longer than max_segments (or of an order outside 2..5) is not an error: like the device form, the solve
+    // marks it CSP_TRAJ_SKIPPED and leaves its block alone (the block still counts in the layout)
     size_t total_co = 0;
+    bool any_skipped = false;
     for (int64_t b = 0; b < B; ++b) {
         const int64_t n = desc->seg_offsets[b + 1] - desc->seg_offsets[b];
-        if (n < 0 || n > desc->max_segments) return CSP_ERR_INVALID_ARG;
+        if (n < 0) return CSP_ERR_INVALID_ARG;
         if (orders[b] >= 1 && n > 0) { const size_t e = (size_t)n * 6 * (size_t)orders[b], pad = f32 ? 4 : 2; total_co += (e + pad - 1) / pad * pad; }
+        any_skipped |= orders[b] >= 1 && n > 0 && (orders[b] > 5 || orders[b] < 2 || n > desc->max_segments);
     }
     csp::HostCall hc(current_device(), st);
     const size_t o_wp = hc.in(waypoints, (size_t)(total_seg + B) * 3 * elt), o_tm = hc.in(times, (size_t)total_seg * elt);
     const size_t o_bc = hc.in(bc, (size_t)(desc->bc_per_trajectory ? B : 1) * 12 * elt);
     const size_t o_so = hc.in(desc->seg_offsets, (size_t)(B + 1) * 8), o_or = hc.in(orders, (size_t)B * 4);
     const size_t o_vw = desc->vel_zero_weight_per_traj ? hc.in(desc->vel_zero_weight_per_traj, (size_t)B * 8) : 0;
+    const size_t o_ci = any_skipped ? hc.in(coeffs, total_co * elt) : 0;   // the caller's bytes of the skipped blocks
     const size_t o_co = hc.out(coeffs, total_co * elt);
     const size_t o_cf = coeff_offsets_out ? hc.out(coeff_offsets_out, (size_t)(B + 1) * 8) : 0;
     const size_t o_st = status ? hc.out(status, (size_t)B * 4) : 0;
@@ -685,7 +695,8 @@ int csp_minsnap_solve_mixed(const csp_minsnap_desc *desc, const int32_t *orders,
     a.seg_off = hc.ptr<const int64_t>(o_so);
     a.vw_per = desc->vel_zero_weight_per_traj ? hc.ptr<const double>(o_vw) : nullptr;
     // skipped trajectories leave their block untouched: the caller's bytes must survive the round trip
-    CSP_HIP(hipMemsetAsync(hc.ptr(o_co), 0, total_co * elt, st));
+    if (any_skipped) CSP_HIP(hipMemcpyAsync(hc.ptr(o_co), hc.ptr(o_ci), total_co * elt, hipMemcpyDeviceToDevice, st));
+    else CSP_HIP(hipMemsetAsync(hc.ptr(o_co), 0, total_co * elt, st));
     hipError_t e = csp::launch_mixed(a, f32, hc.ptr<const int32_t>(o_or), hc.ptr(o_ws), coeff_offsets_out ? hc.ptr<int64_t>(o_cf) : nullptr, st);
     if (e != hipSuccess) return hip_fail(e, "mixed launch");
     CSP_HIP(hc.download());

@@ -2,18 +2,23 @@
 // derivative order; csp_minsnap_solve_mixed, include/csp_minsnap.h).  Everything happens on the device and in the
 // caller's own order -- no gather, no un-permute (blocks 16-byte aligned: block_elems):
 //
-//   1. bucketing (three small kernels): every trajectory gets the key (order, length class) -- the length class is the
-//      number of lanes the workspace-free kernel gives a trajectory (minsnap_chunked_impl.h: 4 segments per lane, rounded
-//      up to a power of two) --; a histogram, an exclusive scan of the coefficient sizes 6 * order * S in CALLER order
-//      (= where each trajectory's block starts in `coeffs`) and a scatter of the trajectory indices into bucket order
-//      (`perm`, longest class first inside an order);
-//   2. one PERSISTENT launch per derivative order (the register budgets differ: 190 / 256 / 392 VGPRs at orders 3 / 4 /
-//      5, so one kernel for all would run everything at one wave per SIMD): wave w takes the work units w, w + grid, ...
-//      of its order -- a unit = 64 lanes of one length class --, reading the inputs and writing the coefficients of
-//      trajectory perm[k] in place.  The launches of the orders run concurrently on forked streams.
+//   1. bucketing (three small kernels): every trajectory gets the key (family, order, length class); a histogram, an
+//      exclusive scan of the coefficient sizes 6 * order * S in CALLER order (= where each trajectory's block starts in
+//      `coeffs`) and a scatter of the trajectory indices into bucket order (`perm`).  The length classes are exact: the
+//      lane-pair family keys on S itself, the chunked family on the number of lanes a trajectory needs (lanes_of: one per
+//      4 segments, not rounded up to a power of two).  A trajectory this path does not serve (order outside 2..5, S = 0,
+//      S above the caller's max_segments) gets no key: CSP_TRAJ_SKIPPED, its block left alone;
+//   2. trajectories of up to 64 segments (every order): ONE persistent launch of the lane-pair sweep
+//      (minsnap_twist_impl.h: a twisted block-LDL^T, two lanes per trajectory, factors recomputed from checkpoints);
+//   3. longer ones (65..256 segments): one persistent launch of the workspace-free chunked kernel per order (the register
+//      budgets differ: 190 / 256 / 392 VGPRs at orders 3 / 4 / 5), wave w taking the work units w, w + grid, ... of its
+//      order (a unit = 64 lanes of one length class).  They run one after the other on the caller's stream; forked
+//      streams per order are opt-in (CSP_MIXED_FORK=1; the event fork / join between hardware queues costs tens of
+//      microseconds).
 //
-// The reference has no batched entry at all (one flight per call, uavPathPlanning.cpp:4423, :4461); per trajectory the
-// arithmetic is that of csp_minsnap_solve_batch on the same order and length class (bit-equal: tests/test_gpu_round3.py).
+// The reference has no batched entry at all (one flight per call, uavPathPlanning.cpp:4423, :4461).  Per trajectory, the
+// chunked family runs the arithmetic of csp_minsnap_solve_batch's chunked kernel, the lane-pair sweep that of the
+// register-resident fixed kernels (tests/test_gpu_round3.py compares the two families).
 #include "minsnap_chunked_impl.h"
 #include "minsnap_mixed.h"
 #include "minsnap_twist_launch.h"

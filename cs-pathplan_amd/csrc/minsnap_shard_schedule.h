@@ -5,7 +5,8 @@
 // on the CPU.
 //
 // Partition: trajectories are independent (minimum_snap.cpp has no cross-trajectory term), so device g of n owns the
-// contiguous range [B g / n, B (g+1) / n) and cuts it into `nchunks` contiguous pieces.  Schedule:
+// contiguous range [B g / n, B (g+1) / n) and cuts it into `nchunks` contiguous pieces (both cuts rounded down to whole
+// slices of 64 trajectories, see shard_range).  Schedule:
 //
 //     for c in chunks:  scatter(c)      one GROUPED point-to-point exchange: the root sends piece (g, c)'s inputs to every
 //                                       peer g (RCCL has no scatter: ncclGroupStart, ncclSend x peers / ncclRecv, ncclGroupEnd);
@@ -27,16 +28,23 @@ struct Piece {
     int64_t lo, hi;   // trajectories [lo, hi) of the batch
 };
 
+// Interior boundaries fall on multiples of SLICE trajectories (the fixed kernels' slice width): a piece then starts on a
+// 16-byte boundary of every per-trajectory array, which the fixed kernels require of their pointers (minsnap_capi.hip,
+// dispatch()).  The last shard and the last piece of a shard take the remainder; pieces and shards may be empty.
+constexpr int64_t SLICE = 64;
+
+inline int64_t slice_floor(int64_t v) { return v / SLICE * SLICE; }
+
 inline void shard_range(int64_t B, int ndev, int g, int64_t &lo, int64_t &hi) {
-    lo = B * g / ndev;
-    hi = B * (g + 1) / ndev;
+    lo = g == 0 ? 0 : slice_floor(B * g / ndev);
+    hi = g == ndev - 1 ? B : slice_floor(B * (g + 1) / ndev);
 }
 
 inline Piece piece_of(int64_t B, int ndev, int nchunks, int g, int c) {
     int64_t lo, hi;
     shard_range(B, ndev, g, lo, hi);
     const int64_t n = hi - lo;
-    return Piece{g, c, lo + n * c / nchunks, lo + n * (c + 1) / nchunks};
+    return Piece{g, c, c == 0 ? lo : lo + slice_floor(n * c / nchunks), c == nchunks - 1 ? hi : lo + slice_floor(n * (c + 1) / nchunks)};
 }
 
 // Transport concept:

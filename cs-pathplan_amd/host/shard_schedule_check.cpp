@@ -3,7 +3,8 @@
 // "Devices" are host buffers, a send/recv pair is a memcpy that happens when its group ends, the "solve" is a known
 // function of the inputs.  Checked: every trajectory's result reaches the root exactly once and is right; a piece is
 // solved only after its inputs arrived and sent back only after it was solved; all scatters are queued before the first
-// solve (what lets the gather of chunk i overlap the solve of chunk i + 1 on the real streams); groups are balanced.
+// solve (what lets the gather of chunk i overlap the solve of chunk i + 1 on the real streams); groups are balanced; the pieces
+// tile the batch exactly once and cut it only on multiples of 64 trajectories.
 // usage: shard_schedule_check B ndev root nchunks   -> exit 0 / 1, one line of statistics on stdout
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +14,7 @@
 #include "../csrc/minsnap_shard_schedule.h"
 
 using csp::shard::Piece;
+constexpr int64_t kSlice = 64;   // the fixed kernels' slice width: what a cut must be a multiple of
 
 struct Recording {
     int64_t B;
@@ -105,6 +107,23 @@ int main(int argc, char **argv) {
         if (plo != hi) { std::fprintf(stderr, "pieces do not cover the shard\n"); return 1; }
     }
     if (covered != r.B || prev_hi != r.B) { std::fprintf(stderr, "shards do not cover the batch\n"); return 1; }
+    // the pieces tile [0, B) exactly once, and every boundary inside the batch is a whole number of slices (the fixed
+    // kernels refuse pointers that are not 16-byte aligned: an odd first trajectory at S = 16 is not)
+    std::vector<int> owners((size_t)r.B, 0);
+    for (int g = 0; g < r.ndev; ++g)
+        for (int c = 0; c < r.nchunks; ++c) {
+            const Piece p = csp::shard::piece_of(r.B, r.ndev, r.nchunks, g, c);
+            if (p.lo < 0 || p.hi > r.B || p.hi < p.lo) { std::fprintf(stderr, "piece (%d, %d) outside the batch\n", g, c); return 1; }
+            for (int64_t e : {p.lo, p.hi})
+                if (e != r.B && e % kSlice != 0) {
+                    std::fprintf(stderr, "piece (%d, %d) = [%lld, %lld) has a boundary off the %lld-trajectory grid\n", g, c, (long long)p.lo,
+                                 (long long)p.hi, (long long)kSlice);
+                    return 1;
+                }
+            for (int64_t i = p.lo; i < p.hi; ++i) ++owners[(size_t)i];
+        }
+    for (int64_t i = 0; i < r.B; ++i)
+        if (owners[(size_t)i] != 1) { std::fprintf(stderr, "trajectory %lld lies in %d pieces\n", (long long)i, owners[(size_t)i]); return 1; }
     const int rc = csp::shard::run(r, r.B, r.ndev, r.root, r.nchunks);
     if (rc != 0) { std::fprintf(stderr, "run() returned %d\n", rc); return 1; }
     for (int64_t i = 0; i < r.B; ++i) {

@@ -6,6 +6,7 @@ The product path (cs-pathplan_amd/) never does.  PARITY UNPINNED: see dense_orac
 import ctypes
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -18,10 +19,11 @@ _dp = ctypes.POINTER(ctypes.c_double)
 
 def build(force=False):
     """Compile dense_oracle.c (gcc) if the shared object is missing or stale."""
-    srcs = [os.path.join(_HERE, f) for f in ("dense_oracle.c", "geo_oracle.c", "alt_oracle.c", "structured_oracle.cpp", "Makefile")]
+    srcs = [os.path.join(_HERE, f) for f in ("dense_oracle.c", "geo_oracle.c", "alt_oracle.c", "structured_oracle.cpp", "Makefile",
+                                             "gen_tables_ld.py", os.path.join("..", "cs-pathplan_amd", "tablegen.py"))]
     if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(f) for f in srcs):
         subprocess.check_call(["make", "-C", _HERE, "-s", "clean"])
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
+        subprocess.check_call(["make", "-C", _HERE, "-s", "PYTHON=" + sys.executable])
     return _LIB_PATH
 
 
@@ -41,6 +43,9 @@ def lib():
             f.restype = ctypes.c_int
             f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_long, _dp, _dp, _dp, ctypes.c_int,
                           ctypes.c_double, ctypes.c_double, _dp, _dp, ctypes.c_int]
+        L.csp_struct_ld_solve_batch.restype = ctypes.c_int
+        L.csp_struct_ld_solve_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_long, _dp, _dp, _dp, ctypes.c_int,
+                                                ctypes.c_double, ctypes.c_void_p, _dp, ctypes.c_int]
         L.csp_struct_solve_batch.restype = ctypes.c_int
         L.csp_struct_solve_batch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_long, _dp, _dp, _dp, ctypes.c_int,
                                              ctypes.c_double, _dp, ctypes.c_int]
@@ -114,16 +119,28 @@ def solve_batch(order, waypoints, times, bc=None, path_weight=0.0, vel_zero_weig
     return coeff, md
 
 
-def struct_solve_batch(order, waypoints, times, bc=None, vel_zero_weight=0.0, nthreads=1, out=None):
+def struct_solve_batch(order, waypoints, times, bc=None, vel_zero_weight=0.0, nthreads=1, out=None, long_double=False,
+                       vel_zero_weight_per_traj=None):
     """The structured CPU solver (structured_oracle.cpp): same problem as solve_batch without the path
-    penalty, block-tridiagonal LDL^T instead of dense inverses.  Returns coeffs [B,S,3,2o]."""
+    penalty, block-tridiagonal LDL^T instead of dense inverses.  Returns coeffs [B,S,3,2o].
+    long_double: the x87 80-bit build with its own tables (the reference for long trajectories), which also takes a
+    per-trajectory velocity-zero weight [B]."""
     waypoints, times = _c(waypoints), _c(times)
     B, S = times.shape
     assert waypoints.shape == (B, S + 1, 3)
-    bc = _c(np.zeros((1, 4, 3)) if bc is None else bc)
+    bc = _c(np.zeros((1, 4, 3)) if bc is None else bc).reshape(-1, 4, 3)
+    assert bc.shape[0] in (1, B)
     coeff = np.zeros((B, S, 3, 2 * order)) if out is None else out
-    rc = lib().csp_struct_solve_batch(order, S, B, _p(waypoints), _p(times), _p(bc), 1 if bc.shape[0] == 1 else 0,
-                                      float(vel_zero_weight), _p(coeff), int(nthreads))
+    bcast = 1 if bc.shape[0] == 1 else 0
+    if long_double:
+        vwp = None if vel_zero_weight_per_traj is None else _c(vel_zero_weight_per_traj, (B,))
+        rc = lib().csp_struct_ld_solve_batch(order, S, B, _p(waypoints), _p(times), _p(bc), bcast, float(vel_zero_weight),
+                                             None if vwp is None else vwp.ctypes.data, _p(coeff), int(nthreads))
+    else:
+        if vel_zero_weight_per_traj is not None:
+            raise ValueError("per-trajectory weights: long_double=True")
+        rc = lib().csp_struct_solve_batch(order, S, B, _p(waypoints), _p(times), _p(bc), bcast, float(vel_zero_weight), _p(coeff),
+                                          int(nthreads))
     if rc:
         raise ValueError("csp_struct_solve_batch rc=%d" % rc)
     return coeff

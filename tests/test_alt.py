@@ -2,10 +2,15 @@
 Eigen::SimplicialLDLT sites, uavPathPlanning.cpp:1575-1827).  PARITY UNPINNED (no Eigen, no goldens):
 the C oracle (dense Cholesky) is pinned against an independent numpy restatement here; the HIP
 kernels (banded LDL^T) are compared with the oracle on the GPU box."""
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
 import oracle
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _problem(rng, n, with_gaps=True):
@@ -134,6 +139,17 @@ def test_hip_lane_and_wave_kernels_agree(csp):
     assert np.array_equal(z_wave, z_lane[sel])
     assert np.array_equal(g_wave, g_lane[sel])
     assert np.array_equal(s_wave, s_lane[pick])
+
+
+def test_cyclic_reduction_workspace_regions_fit(tmp_path):
+    """The workspace region of every problem of a cyclic-reduction call (cs-pathplan_amd/csrc/alt_cr_layout.h: solution, block
+    rows, active flags) stays clear of its neighbour's and inside csp_alt_workspace_bytes, for every length 1..5000 and the
+    largest batch that path takes.  14 doubles per sample alone do not hold a one-sample problem's 18."""
+    exe = str(tmp_path / "alt_cr_layout_check")
+    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", "-Werror", os.path.join(ROOT, "cs-pathplan_amd", "host", "alt_cr_layout_check.cpp"), "-o", exe])
+    r = subprocess.run([exe, "5000"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.startswith("ok")
 
 
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 64, 300])

@@ -166,8 +166,11 @@ def test_mixed_entry_edge_cases(csp, oracle_mod):
                               max_segments=n, force_generic=n <= 0)
         if n <= 64 and not (o == 5 and n > 32):
             ref, _ = oracle_mod.solve(o, wps[i], bc[i, [0, 1]], bc[i, [2, 3]], tms[i], 0.0, float(vw[i]), long_double=o == 5)
-            synth.parity_gate(got, ref, 1e-6 if o == 5 else 5e-8, ("mixed entry vs oracle", i, o, n))
-        synth.parity_gate(got, one.coeffs, 5e-5 if o == 5 else 1e-8, ("mixed entry vs single ragged call", i, o, n))
+            _, nw = synth.parity_gate(got, ref, 1e-6 if o == 5 else 5e-8, ("mixed entry vs oracle", i, o, n))
+            assert nw <= 1e-6, ("mixed entry vs oracle, norm-wise (north star)", i, o, n, nw)
+        _, nw = synth.parity_gate(got, one.coeffs, 5e-5 if o == 5 else 1e-8, ("mixed entry vs single ragged call", i, o, n))
+        if o == 5:   # beside the widened order-5 gate: the north-star figure, norm-wise
+            assert nw <= 1e-6, ("mixed entry vs single ragged call, norm-wise (north star)", i, o, n, nw)
     # device form, unsupported trajectories among good ones
     bad_orders = orders.copy()
     bad_orders[3], bad_orders[10] = 1, 6

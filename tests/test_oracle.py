@@ -198,3 +198,51 @@ def test_closed_form_is_the_minimiser_of_the_constrained_qp():
         for k in worst:
             worst[k] = max(worst[k], e[k])
     print("closed form vs the 60-digit KKT solution, worst per-power error:", worst)
+
+
+# worst per-power error of the long-double structured solver against the 80-bit dense oracle (S <= 40, random boundary
+# conditions and weights), measured on the CPU: 1.6e-17, 8.7e-17, 3.9e-16, 1.1e-12, 6.0e-9 at orders 1..5 -- what grows is the
+# dense oracle's own rounding (O(S^3) elimination of an ill-conditioned KKT matrix), which the 60-digit test below does not see
+LD_VS_DENSE_TOL = {1: 1e-15, 2: 1e-15, 3: 5e-15, 4: 1e-11, 5: 5e-8}
+
+
+@pytest.mark.parametrize("order", [1, 2, 3, 4, 5])
+def test_long_double_structured_solver_matches_the_80_bit_dense_oracle(order):
+    """oracle/structured_oracle.cpp's long-double build (the reference of the long-trajectory GPU tests) against the 80-bit
+    dense restatement, trajectory by trajectory: per-trajectory boundary conditions, per-trajectory velocity-zero weights
+    (one of them 0), a shared boundary condition, S = 1..40."""
+    rng = np.random.default_rng(70 + order)
+    worst = 0.0
+    for S in (1, 2, 3, 7, 16, 17, 25, 40):
+        B = 5
+        wp, tm = synth.make_batch(B, S, config_id=7)
+        bc = rng.normal(size=(B, 4, 3))
+        vw = rng.uniform(0.0, 0.3, size=B)
+        vw[0] = 0.0
+        got = oracle.struct_solve_batch(order, wp, tm, bc, long_double=True, vel_zero_weight_per_traj=vw, nthreads=2)
+        for b in range(B):
+            ref, _ = oracle.solve(order, wp[b], bc[b, [0, 1]], bc[b, [2, 3]], tm[b], 0.0, float(vw[b]), long_double=True)
+            worst = max(worst, synth.rel_err_per_power(got[b], ref.reshape(S, 3, 2 * order)))
+        shared = oracle.struct_solve_batch(order, wp, tm, bc[:1], vel_zero_weight=0.05, long_double=True)
+        ref, _ = oracle.solve_batch(order, wp, tm, bc[:1], vel_zero_weight=0.05, long_double=True)
+        worst = max(worst, synth.rel_err_per_power(shared, ref))
+    print("order %d: long-double structured vs 80-bit dense, worst per power %.2e" % (order, worst))
+    assert worst < LD_VS_DENSE_TOL[order], (order, worst)
+
+
+def test_long_double_structured_solver_against_the_60_digit_kkt_solution():
+    """F8 without the path penalty (which the structured solver does not have): the long-double structured solve agrees
+    per power with the 60-digit KKT solution to 5.1e-15 at worst (order 5, 8 segments) -- far inside what the GPU tests
+    ask of it."""
+    worst, n = 0.0, 0
+    for c in load_cases("F8_kkt_mpmath.json"):
+        if c["path_weight"] > 0:
+            continue
+        S, m = c["segments"], 2 * c["order"]
+        got = oracle.struct_solve_batch(c["order"], c["path"][None], c["time"][None], c["bc"][None], vel_zero_weight=c["vel_zero_weight"],
+                                        long_double=True)
+        e = synth.rel_err_per_power(got[0], c["coeff"].reshape(S, 3, m))
+        assert e < 1e-13, (c["name"], e)
+        worst, n = max(worst, e), n + 1
+    assert n >= 10
+    print("long-double structured vs the 60-digit KKT solution (%d cases), worst per power %.2e" % (n, worst))
