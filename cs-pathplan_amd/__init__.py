@@ -40,6 +40,7 @@ TRAJ_OK, TRAJ_NONFINITE, TRAJ_NOT_SPD, TRAJ_SKIPPED = 0, 1, 2, 4
 
 EXPORTED_SYMBOLS = (
     "csp_minsnap_solve_batch", "csp_minsnap_solve_batch_sharded", "csp_minsnap_workspace_bytes", "csp_minsnap_time_alloc_batch",
+    "csp_minsnap_solve_batch_vjp", "csp_minsnap_vjp_workspace_bytes",
     "csp_minsnap_solve_mixed", "csp_minsnap_mixed_workspace_bytes", "csp_minsnap_solve_multi",
     "csp_minsnap_plan_batch", "csp_minsnap_plan_workspace_bytes", "csp_minsnap_sample_batch",
     "csp_minsnap_generate_batch", "csp_minsnap_sample_capacity",
@@ -80,6 +81,10 @@ if not os.path.exists(LIB_PATH):
 _lib = ctypes.CDLL(LIB_PATH)
 _lib.csp_minsnap_solve_batch.restype = ctypes.c_int
 _lib.csp_minsnap_solve_batch.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]
+_lib.csp_minsnap_solve_batch_vjp.restype = ctypes.c_int
+_lib.csp_minsnap_solve_batch_vjp.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 9 + [ctypes.c_size_t, ctypes.c_void_p]
+_lib.csp_minsnap_vjp_workspace_bytes.restype = ctypes.c_size_t
+_lib.csp_minsnap_vjp_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
 _lib.csp_minsnap_solve_batch_sharded.restype = ctypes.c_int
 _lib.csp_minsnap_solve_batch_sharded.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 6 + [ctypes.c_int]
 _lib.csp_minsnap_workspace_bytes.restype = ctypes.c_size_t
@@ -311,6 +316,168 @@ def solve_batch(waypoints, times, bc=None, order=4, path_weight=0.0, vel_zero_we
             None, 0, None)
     _check(rc)
     return Result(out, md, stt, kernel_name(desc))
+
+
+def vjp_workspace_bytes(desc):
+    return int(_lib.csp_minsnap_vjp_workspace_bytes(ctypes.byref(desc)))
+
+
+class VjpResult:
+    """Gradients of solve_batch_vjp; a gradient that was not asked for is None."""
+    __slots__ = ("waypoints", "times", "bc", "status")
+
+    def __init__(self, waypoints, times, bc, status):
+        self.waypoints, self.times, self.bc, self.status = waypoints, times, bc, status
+
+
+_VJP_WANT = ("waypoints", "times", "bc")
+
+
+def solve_batch_vjp(waypoints, times, grad_coeffs, bc=None, order=4, vel_zero_weight=0.0, seg_offsets=None,
+                    max_segments=None, vel_zero_weight_per_traj=None, want=_VJP_WANT, want_status=False,
+                    workspace=None, stream=None):
+    """Vector-Jacobian product of solve_batch (csp_minsnap_solve_batch_vjp): given grad_coeffs = dL/dcoeffs in the layout
+    of solve_batch's coefficients, returns VjpResult(dL/dwaypoints, dL/dtimes, dL/dbc, status) for the names in `want`.
+    Inputs as in solve_batch (no path penalty): numpy arrays -> CSP_MEM_HOST, torch CUDA tensors -> CSP_MEM_DEVICE.
+    dL/dbc has the shape of bc after reshaping to [-1,4,3]: [1,4,3] summed over the batch, or [B,4,3]; bc=None is
+    treated as a shared zero bc."""
+    want = tuple(want)
+    for w in want:
+        if w not in _VJP_WANT:
+            raise ValueError("want: a subset of %r" % (_VJP_WANT,))
+    ragged = seg_offsets is not None
+    m = 2 * int(order)
+    if _is_torch(waypoints):
+        import torch
+        if not waypoints.is_cuda:
+            raise ValueError("torch inputs must be CUDA tensors (use numpy arrays for host memory)")
+        tdt = waypoints.dtype
+        dtype = DTYPE_F32 if tdt == torch.float32 else DTYPE_F64
+        dev = waypoints.device
+        waypoints, times = waypoints.contiguous(), times.to(tdt).contiguous()
+        gco = grad_coeffs.to(device=dev, dtype=tdt).contiguous()
+        if gco.data_ptr() % 16:
+            gco = gco.clone()
+        if ragged:
+            seg_offsets = seg_offsets.to(device=dev, dtype=torch.int64).contiguous()
+            B, S, total = seg_offsets.numel() - 1, 0, times.numel()
+            if max_segments is None:
+                max_segments = int((seg_offsets[1:] - seg_offsets[:-1]).max().item()) if B else 1
+        else:
+            B, S = times.shape
+            total = B * S
+        if gco.numel() != total * 3 * m:
+            raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % (total * 3 * m))
+        bc = torch.zeros((1, 4, 3), dtype=tdt, device=dev) if bc is None else bc.to(tdt).contiguous().reshape(-1, 4, 3)
+        if bc.shape[0] not in (1, B):
+            raise ValueError("bc must be [4,3], [1,4,3] or [B,4,3]")
+        per = bc.shape[0] == B
+        gwp = torch.empty_like(waypoints) if "waypoints" in want else None
+        gtm = torch.empty_like(times) if "times" in want else None
+        gbc = torch.empty_like(bc) if "bc" in want else None
+        stt = torch.empty(B, dtype=torch.int32, device=dev) if want_status else None
+        vwp = None
+        if vel_zero_weight_per_traj is not None:
+            vwp = vel_zero_weight_per_traj.to(device=dev, dtype=torch.float64).contiguous()
+        desc = make_desc(order, B, S, dtype, 0.0, vel_zero_weight, MEM_DEVICE, per,
+                         seg_offsets.data_ptr() if ragged else None, max_segments or 0,
+                         vwp.data_ptr() if vwp is not None else None, dev.index if dev.index is not None else -1, 0)
+        need = vjp_workspace_bytes(desc)
+        if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
+            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _check(_lib.csp_minsnap_solve_batch_vjp(
+            ctypes.byref(desc), waypoints.data_ptr(), times.data_ptr(), bc.data_ptr(), gco.data_ptr(), ptr(gwp), ptr(gtm),
+            ptr(gbc), ptr(stt), workspace.data_ptr() if need else None, need, ctypes.c_void_p(st)))
+        return VjpResult(gwp, gtm, gbc, stt)
+
+    waypoints = np.asarray(waypoints)
+    dtype = DTYPE_F32 if waypoints.dtype == np.float32 else DTYPE_F64
+    npdt = _np_dtype(dtype)
+    waypoints = np.ascontiguousarray(waypoints, dtype=npdt)
+    times = np.ascontiguousarray(times, dtype=npdt)
+    gco = np.ascontiguousarray(grad_coeffs, dtype=npdt)
+    if ragged:
+        seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.int64)
+        B, S, total = seg_offsets.shape[0] - 1, 0, times.shape[0]
+        if max_segments is None:
+            max_segments = int(np.max(np.diff(seg_offsets))) if B else 1
+    else:
+        B, S = times.shape
+        total = B * S
+    if gco.size != total * 3 * m:
+        raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % (total * 3 * m))
+    bc = np.zeros((1, 4, 3), dtype=npdt) if bc is None else np.ascontiguousarray(bc, dtype=npdt).reshape(-1, 4, 3)
+    if bc.shape[0] not in (1, B):
+        raise ValueError("bc must be [4,3], [1,4,3] or [B,4,3]")
+    per = bc.shape[0] == B
+    gwp = np.empty_like(waypoints) if "waypoints" in want else None
+    gtm = np.empty_like(times) if "times" in want else None
+    gbc = np.empty_like(bc) if "bc" in want else None
+    stt = np.empty(B, dtype=np.int32) if want_status else None
+    vwp = None
+    if vel_zero_weight_per_traj is not None:
+        vwp = np.ascontiguousarray(vel_zero_weight_per_traj, dtype=np.float64)
+    desc = make_desc(order, B, S, dtype, 0.0, vel_zero_weight, MEM_HOST, per,
+                     seg_offsets.ctypes.data if ragged else None, max_segments or 0,
+                     vwp.ctypes.data if vwp is not None else None, -1, 0)
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    _check(_lib.csp_minsnap_solve_batch_vjp(
+        ctypes.byref(desc), waypoints.ctypes.data, times.ctypes.data, bc.ctypes.data, gco.ctypes.data, ptr(gwp), ptr(gtm),
+        ptr(gbc), ptr(stt), None, 0, None))
+    return VjpResult(gwp, gtm, gbc, stt)
+
+
+def _make_autograd_fn():
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class SolveBatchFn(torch.autograd.Function):
+        """coeffs = solve_batch(waypoints, times, bc); backward = solve_batch_vjp for the inputs that need it."""
+
+        @staticmethod
+        def forward(ctx, waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj):
+            r = solve_batch(waypoints.detach(), times.detach(), None if bc is None else bc.detach(), order=order,
+                            vel_zero_weight=vel_zero_weight, seg_offsets=seg_offsets, max_segments=max_segments,
+                            vel_zero_weight_per_traj=vel_zero_weight_per_traj)
+            ctx.save_for_backward(waypoints, times, bc, seg_offsets, vel_zero_weight_per_traj)
+            ctx.order, ctx.vel_zero_weight, ctx.max_segments = order, vel_zero_weight, max_segments
+            return r.coeffs
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_coeffs):
+            waypoints, times, bc, seg_offsets, vwp = ctx.saved_tensors
+            need_wp, need_tm, need_bc = ctx.needs_input_grad[:3]
+            want = tuple(n for n, f in zip(_VJP_WANT, (need_wp, need_tm, need_bc)) if f)
+            if not want:
+                return (None,) * 8
+            g = solve_batch_vjp(waypoints, times, grad_coeffs, bc=bc, order=ctx.order, vel_zero_weight=ctx.vel_zero_weight,
+                                seg_offsets=seg_offsets, max_segments=ctx.max_segments, vel_zero_weight_per_traj=vwp,
+                                want=want)
+            gwp = g.waypoints.to(waypoints.dtype) if need_wp else None
+            gtm = g.times.to(times.dtype) if need_tm else None
+            gbc = g.bc.reshape(bc.shape).to(bc.dtype) if need_bc else None
+            return gwp, gtm, gbc, None, None, None, None, None
+
+    return SolveBatchFn
+
+
+_autograd_fn = None
+
+
+def solve_batch_autograd(waypoints, times, bc=None, order=4, vel_zero_weight=0.0, seg_offsets=None, max_segments=None,
+                         vel_zero_weight_per_traj=None):
+    """solve_batch as a differentiable torch op (CUDA tensors): returns the coefficients -- bit-equal to
+    solve_batch(...).coeffs -- with a grad_fn when waypoints, times or bc require grad.  The backward pass is
+    csp_minsnap_solve_batch_vjp for the inputs that need a gradient; it is first-order only (once_differentiable).
+    No path penalty; no gradient with respect to the weights."""
+    global _autograd_fn
+    if _autograd_fn is None:
+        _autograd_fn = _make_autograd_fn()
+    return _autograd_fn.apply(waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments,
+                              vel_zero_weight_per_traj)
 
 
 class PreparedMulti:

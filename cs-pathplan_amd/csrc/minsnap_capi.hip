@@ -1252,3 +1252,109 @@ int csp_minsnap_generate_batch(const csp_minsnap_desc *desc, const void *waypoin
 void csp_minsnap_release_cached_memory(void) { csp::arena_free_idle(); }
 
 }  // extern "C"
+
+namespace {
+
+// csp_minsnap_solve_batch_vjp's own limits on top of validate(): no path penalty (t* is a discrete arg-max and the
+// penalty's chord point depends on T), orders 2..5, trajectory-major coefficients, fp64 arithmetic.
+int validate_vjp(const csp_minsnap_desc *d, Shape &s) {
+    int rc = validate(d, s);
+    if (rc != CSP_OK) return rc;
+    if (d->order < 2) return CSP_ERR_UNSUPPORTED;
+    if (d->path_weight != 0.0) return CSP_ERR_UNSUPPORTED;
+    if (d->flags & (CSP_FLAG_SEGMENT_MAJOR | CSP_FLAG_F32_ARITH)) return CSP_ERR_UNSUPPORTED;
+    return CSP_OK;
+}
+
+size_t vjp_ws_bytes(const csp_minsnap_desc *d, const Shape &s, size_t *part_off) {
+    const size_t factors = align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::vjp_ws_entries(s.order) * (size_t)s.B * 8, 256);
+    if (part_off) *part_off = factors;
+    return factors + (d->bc_per_trajectory ? 0 : 12 * (size_t)csp::vjp_blocks(s.B) * 8);
+}
+
+int dispatch_vjp(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const void *bc, const void *gco,
+                 void *gwp, void *gtm, void *gbc, int32_t *status, const int64_t *seg_off, const double *vw_per, void *ws,
+                 size_t ws_size, hipStream_t st) {
+    size_t part_off = 0;
+    const size_t need = vjp_ws_bytes(d, s, &part_off);
+    if (need > 0 && (!ws || ws_size < need)) return CSP_ERR_WORKSPACE;
+    if ((uintptr_t)ws & 7u) return CSP_ERR_WORKSPACE;
+    if ((uintptr_t)gco & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // p_bar records are read as 2-element vectors
+    csp::VjpArgs a;
+    a.wp = wp; a.times = tm; a.bc = bc; a.grad_coeffs = gco;
+    a.grad_wp = gwp; a.grad_times = gtm; a.grad_bc = gbc; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.ws = ws;
+    a.bc_part = (gbc && !d->bc_per_trajectory) ? (void *)((char *)ws + part_off) : nullptr;
+    a.vw_per = vw_per;
+    a.vel_zero_weight = d->vel_zero_weight;
+    a.B = s.B; a.S = s.S; a.order = s.order; a.bc_per_traj = d->bc_per_trajectory ? 1 : 0;
+    hipError_t e = csp::launch_vjp(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, "vjp kernel launch");
+    return CSP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t csp_minsnap_vjp_workspace_bytes(const csp_minsnap_desc *desc) {
+    Shape s;
+    if (validate_vjp(desc, s) != CSP_OK) return 0;
+    return vjp_ws_bytes(desc, s, nullptr);
+}
+
+int csp_minsnap_solve_batch_vjp(const csp_minsnap_desc *desc, const void *waypoints, const void *times,
+                                const void *bc, const void *grad_coeffs, void *grad_waypoints,
+                                void *grad_times, void *grad_bc, int32_t *status,
+                                void *workspace, size_t workspace_bytes, void *hip_stream) {
+    Shape s;
+    int rc = validate_vjp(desc, s);
+    if (rc != CSP_OK) return rc;
+    if (s.B == 0) return CSP_OK;
+    if (!waypoints || !times || !bc || !grad_coeffs) return CSP_ERR_INVALID_ARG;
+    rc = select_device(desc->device_id);
+    if (rc != CSP_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+
+    if (desc->mem_space == CSP_MEM_DEVICE)
+        return dispatch_vjp(desc, s, waypoints, times, bc, grad_coeffs, grad_waypoints, grad_times, grad_bc, status,
+                            desc->seg_offsets, desc->vel_zero_weight_per_traj, workspace, workspace_bytes, st);
+
+    // CSP_MEM_HOST: staged through the cached arena, synchronous (as csp_minsnap_solve_batch)
+    int64_t total_seg;
+    if (s.ragged) {
+        total_seg = desc->seg_offsets[s.B];
+        for (int64_t b = 0; b < s.B; ++b) {
+            const int64_t n = desc->seg_offsets[b + 1] - desc->seg_offsets[b];
+            if (n < 0 || n > s.Smax) return CSP_ERR_INVALID_ARG;
+        }
+    } else {
+        total_seg = s.B * (int64_t)s.S;
+    }
+    const size_t m = 2 * (size_t)s.order;
+    const size_t n_wp = (size_t)(total_seg + s.B) * 3 * s.elt, n_tm = (size_t)total_seg * s.elt;
+    const size_t n_bc = (size_t)(desc->bc_per_trajectory ? s.B : 1) * 12 * s.elt;
+    const size_t n_co = (size_t)total_seg * 3 * m * s.elt;
+    const size_t n_ws = vjp_ws_bytes(desc, s, nullptr);
+    csp::HostCall hc(current_device(), st);
+    const size_t o_wp = hc.in(waypoints, n_wp), o_tm = hc.in(times, n_tm), o_bc = hc.in(bc, n_bc);
+    const size_t o_gc = hc.in(grad_coeffs, n_co);
+    const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
+    const size_t o_vw = desc->vel_zero_weight_per_traj ? hc.in(desc->vel_zero_weight_per_traj, (size_t)s.B * 8) : 0;
+    const size_t o_gw = grad_waypoints ? hc.out(grad_waypoints, n_wp) : 0;
+    const size_t o_gt = grad_times ? hc.out(grad_times, n_tm) : 0;
+    const size_t o_gb = grad_bc ? hc.out(grad_bc, n_bc) : 0;
+    const size_t o_st = status ? hc.out(status, (size_t)s.B * 4) : 0;
+    const size_t o_ws = hc.scratch(n_ws);
+    CSP_HIP(hc.upload());
+    rc = dispatch_vjp(desc, s, hc.ptr(o_wp), hc.ptr(o_tm), hc.ptr(o_bc), hc.ptr(o_gc), grad_waypoints ? hc.ptr(o_gw) : nullptr,
+                      grad_times ? hc.ptr(o_gt) : nullptr, grad_bc ? hc.ptr(o_gb) : nullptr,
+                      status ? hc.ptr<int32_t>(o_st) : nullptr, s.ragged ? hc.ptr<const int64_t>(o_so) : nullptr,
+                      desc->vel_zero_weight_per_traj ? hc.ptr<const double>(o_vw) : nullptr, hc.ptr(o_ws), n_ws, st);
+    if (rc != CSP_OK) return rc;
+    CSP_HIP(hc.download());
+    return CSP_OK;
+}
+
+}  // extern "C"

@@ -83,6 +83,30 @@ bool span_supported(int order, int Smax, bool f32_arith, double path_weight, boo
 int span_lanes_log2(int Smax);
 hipError_t launch_span(const GenericArgs &a, bool f32, int Smax, hipStream_t st);
 
+// Reverse mode of the solve (minsnap_vjp.hip): orders 2..5, uniform or ragged, f64 storage or f32 storage with f64
+// arithmetic, zero-velocity penalty; no path penalty.  One lane per trajectory, workgroups of 64.
+struct VjpArgs {
+    const void *wp, *times, *bc;   // as GenericArgs
+    const void *grad_coeffs;       // [B][S][3][2o] (trajectory-major)
+    void *grad_wp;                 // [B][S+1][3] or null
+    void *grad_times;              // [B][S] or null
+    void *grad_bc;                 // [B][4][3] (bc_per_traj) or [4][3] summed over the batch, or null
+    int32_t *status;               // [B] or null
+    const int64_t *seg_off;        // ragged prefix sums or null
+    void *ws;                      // f64 [(Smax-1)][(o-1)^2 + 6(o-1)][B]
+    void *bc_part;                 // f64 [12][vjp_blocks(B)]: per-workgroup partials of a shared bc's gradient
+    const double *vw_per;          // [B] or null
+    double vel_zero_weight;
+    int64_t B;
+    int S;                         // uniform S (ignored when seg_off != null)
+    int order;
+    int bc_per_traj;
+};
+constexpr int CSP_TRAJ_NONFINITE_BIT = 1, CSP_TRAJ_NOT_SPD_BIT = 2;   // include/csp_minsnap.h CSP_TRAJ_*
+inline int64_t vjp_blocks(int64_t B) { return (B + 63) / 64; }
+inline size_t vjp_ws_entries(int order) { const int n = order - 1; return (size_t)(n * n + 6 * n); }
+hipError_t launch_vjp(const VjpArgs &a, bool f32, hipStream_t st);
+
 struct TimeAllocArgs {
     const void *wp;
     void *times;

@@ -1,0 +1,435 @@
+// minsnap_vjp.hip -- reverse mode of the solve: the vector-Jacobian product of csp_minsnap_solve_batch
+// (orders 2..5, uniform or ragged, fp64 storage or fp32 storage with fp64 arithmetic, zero-velocity penalty).
+//
+// Given p_bar = dL/dcoeffs, per axis:
+//   d_bar_j = M(T_j)^-T p_bar_j                          (endpoint-derivative space, no inverse at run time)
+//   K_ff lambda = d_bar_free                             (the forward's R_PP, shared by the three axes)
+//   grad at a fixed slot  = d_bar_F - sum_j (Qt^w_j lambda~_j)_F
+//   T_bar_j = (1/T_j) [ sum_a deriv_a d_a d_bar_a - sum_i pow_i p_i p_bar_i
+//                       - sum_ab (1-2o+deriv_a+deriv_b) lambda~_a Qt_ab d_b ]
+// The layout follows minsnap_generic.hip: one lane per trajectory, the block-LDL^T factors in a coalesced
+// [waypoint][entry][trajectory] workspace, the next step's inputs requested one step ahead.  The primal is
+// re-solved in the same factorisation (6 right-hand sides: 3 primal, 3 adjoint) instead of being rebuilt from
+// the forward's coefficients, which may be fp32 and lose digits at large T (cond(M)).
+// p_bar is read twice: once forwards (free slots of d_bar for the adjoint right-hand side) and once in the back
+// substitution (T_bar and the fixed-slot gradients).  Storing what the back pass needs would cost as many
+// workspace bytes, written and read, as the one extra read.
+// A shared bc's gradient is reduced over the batch in a fixed order (in-wave tree, then one small kernel over
+// the per-workgroup partials), so results are bit-identical run to run; no atomics.
+#include "minsnap_device.h"
+#include "minsnap_launch.h"
+
+namespace csp {
+
+namespace {
+
+template <typename IO, typename R>
+__device__ __forceinline__ void vload3(const IO *p, R (&v)[3]) { v[0] = R(p[0]); v[1] = R(p[1]); v[2] = R(p[2]); }
+
+// One segment's p_bar record [3][2O] as 16-byte (f64) or 8-byte (f32) vector loads: record bases are multiples of
+// 2O*sizeof(IO) bytes from a 16-byte (f64) / 8-byte (f32) aligned array (checked by the C-ABI).
+template <int O, typename IO, typename R>
+__device__ __forceinline__ void load_rec(const IO *src, R (&q)[3][2 * O]) {
+    typedef IO vec2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax)
+#pragma unroll
+        for (int i = 0; i < 2 * O; i += 2) {
+            const vec2 v = *reinterpret_cast<const vec2 *>(src + ax * 2 * O + i);
+            q[ax][i] = R(v.x);
+            q[ax][i + 1] = R(v.y);
+        }
+}
+
+// d_bar[a] = T^deriv_a sum_i G[i][a] T^-pow_i p_bar[i]  (= M(T)^-T p_bar), for the slots a in [A0, A1)
+template <int O, int A0, int A1, typename R>
+__device__ __forceinline__ void dbar_axis(const R (&pb)[2 * O], const R (&tp)[O], const R (&ip)[2 * O], R (&db)[2 * O]) {
+    constexpr int M = 2 * O;
+    R ph[M];
+#pragma unroll
+    for (int i = 0; i < M; ++i) ph[i] = pb[i] * ip[M - 1 - i];
+#pragma unroll
+    for (int a = A0; a < A1; ++a) {
+        R acc = R(0);
+#pragma unroll
+        for (int i = 0; i < M; ++i) {
+            constexpr double zero = 0.0;
+            if (Tab<O>::G(i, a) != zero) acc = fma_<R>(R(Tab<O>::G(i, a)), ph[i], acc);
+        }
+        db[a] = acc * tp[a % O];
+    }
+}
+
+template <int O, typename R> __device__ __forceinline__ void powers(R T, R (&tp)[O], R (&ip)[2 * O]) {
+    tp[0] = R(1);
+#pragma unroll
+    for (int e = 1; e < O; ++e) tp[e] = tp[e - 1] * T;
+    ip[0] = R(1);
+    ip[1] = fast_rcp(T);
+#pragma unroll
+    for (int e = 2; e < 2 * O; ++e) ip[e] = ip[e - 1] * ip[1];
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+}  // namespace
+
+template <int O, typename IO, typename R>
+__global__ void __launch_bounds__(64) minsnap_vjp_kernel(VjpArgs a) {
+    constexpr int N = O - 1;
+    constexpr int M = 2 * O;
+    constexpr int E = N * N + 6 * N;   // workspace entries per interior waypoint: W (N x N), z (N x 6)
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t seg0 = 0;
+    int S = 0;
+    if (b < a.B) {
+        if (a.seg_off) { seg0 = a.seg_off[b]; S = (int)(a.seg_off[b + 1] - seg0); }
+        else { seg0 = b * (int64_t)a.S; S = a.S; }
+    }
+    R gbc[4][3];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) gbc[r][ax] = R(0);
+    int status = 0;
+    if (b < a.B && S < 1) {   // an empty ragged trajectory: its one waypoint (and its bc) get zero gradients
+        if (a.grad_wp) {
+            IO *gwp = (IO *)a.grad_wp + (seg0 + b) * 3;
+            gwp[0] = IO(0); gwp[1] = IO(0); gwp[2] = IO(0);
+        }
+        if (a.grad_bc && a.bc_per_traj)
+            for (int e = 0; e < 12; ++e) ((IO *)a.grad_bc)[b * 12 + e] = IO(0);
+    }
+    if (S >= 1) {
+        const IO *wp = (const IO *)a.wp + (seg0 + b) * 3;
+        const IO *tm = (const IO *)a.times + seg0;
+        const IO *gco = (const IO *)a.grad_coeffs + seg0 * 3 * M;
+        IO *gwp = a.grad_wp ? (IO *)a.grad_wp + (seg0 + b) * 3 : nullptr;
+        IO *gtm = a.grad_times ? (IO *)a.grad_times + seg0 : nullptr;
+        const IO *bc = (const IO *)a.bc + (a.bc_per_traj ? b * 12 : 0);
+        // fixed boundary derivatives: velocity (order >= 2), acceleration (order >= 3), higher ones zero
+        R x0[N][3], xS[N][3];
+#pragma unroll
+        for (int r = 0; r < N; ++r)
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                x0[r][ax] = r == 0 ? R(bc[0 * 3 + ax]) : r == 1 ? R(bc[2 * 3 + ax]) : R(0);
+                xS[r][ax] = r == 0 ? R(bc[1 * 3 + ax]) : r == 1 ? R(bc[3 * 3 + ax]) : R(0);
+            }
+        R *ws = (R *)a.ws + b;
+        const R vw = (R)(a.vw_per ? a.vw_per[b] : a.vel_zero_weight);
+
+        // ---- forward sweep: block-LDL^T of R_PP with 3 primal and 3 adjoint right-hand sides ----
+        if (S > 1) {
+            R W[N][N], z[N][6];
+#pragma unroll
+            for (int r = 0; r < N; ++r) {
+#pragma unroll
+                for (int c = 0; c < N; ++c) W[r][c] = R(0);
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) { z[r][ax] = x0[r][ax]; z[r][3 + ax] = R(0); }
+            }
+            R Pp[3], Pc[3], Pn[3], Pnn[3] = {R(0), R(0), R(0)};
+            vload3<IO, R>(wp, Pp);
+            vload3<IO, R>(wp + 3, Pc);
+            vload3<IO, R>(wp + 6, Pn);
+            R Tn = R(tm[1]), Tnn = R(1);
+            R pbn[3][M], pbnn[3][M];
+            // segment 0: the end part of its d_bar is the left contribution of waypoint 1
+            R dend[N][3];
+            {
+                R pb0[3][M], tp[O], ip[M];
+                load_rec<O, IO, R>(gco, pb0);
+                load_rec<O, IO, R>(gco + 3 * M, pbn);
+                const R T0 = R(tm[0]);
+                powers<O, R>(T0, tp, ip);
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) {
+                    R db[M];
+                    dbar_axis<O, O + 1, M, R>(pb0[ax], tp, ip, db);
+#pragma unroll
+                    for (int r = 0; r < N; ++r) dend[r][ax] = db[O + 1 + r];
+                }
+            }
+            SegBlocks<O, R> left, right;
+            seg_blocks<O, R, false>(R(tm[0]), vw, R(0), 0, Pp, Pc, left);
+            for (int k = 1; k < S; ++k) {
+                if (k + 1 < S) {  // prefetch waypoint k+2, time k+1 and p_bar of segment k+1
+                    vload3<IO, R>(wp + 3 * (k + 2), Pnn);
+                    Tnn = R(tm[k + 1]);
+                    load_rec<O, IO, R>(gco + (int64_t)(k + 1) * 3 * M, pbnn);
+                }
+                seg_blocks<O, R, false>(Tn, vw, R(0), 0, Pc, Pn, right);
+                R dstart[N][3], dnext[N][3];
+                {
+                    R tp[O], ip[M];
+                    powers<O, R>(Tn, tp, ip);
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax) {
+                        R db[M];
+                        dbar_axis<O, 1, O, R>(pbn[ax], tp, ip, db);
+                        dbar_axis<O, O + 1, M, R>(pbn[ax], tp, ip, db);
+#pragma unroll
+                        for (int r = 0; r < N; ++r) { dstart[r][ax] = db[1 + r]; dnext[r][ax] = db[O + 1 + r]; }
+                    }
+                }
+                R A[N][N], Bm[N][N + 6];
+#pragma unroll
+                for (int r = 0; r < N; ++r) {
+#pragma unroll
+                    for (int c = 0; c < N; ++c) {
+                        R v = left.ee[r][c] + right.ss[r][c];
+#pragma unroll
+                        for (int j = 0; j < N; ++j) v = fma_<R>(-left.se[j][r], W[j][c], v);
+                        A[r][c] = v;
+                        Bm[r][c] = right.se[r][c];
+                    }
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax) {
+                        R v = left.ep0[r] * Pp[ax];
+                        v = fma_<R>(left.ep1[r], Pc[ax], v);
+                        v = fma_<R>(right.sp0[r], Pc[ax], v);
+                        v = fma_<R>(right.sp1[r], Pn[ax], v);
+                        R u = dend[r][ax] + dstart[r][ax];
+#pragma unroll
+                        for (int j = 0; j < N; ++j) {
+                            v = fma_<R>(left.se[j][r], z[j][ax], v);
+                            u = fma_<R>(-left.se[j][r], z[j][3 + ax], u);
+                        }
+                        Bm[r][N + ax] = -v;
+                        Bm[r][N + 3 + ax] = u;
+                    }
+                }
+                const R piv = spd_solve<N, N + 6, R>(A, Bm);
+                if (!(piv > R(0))) status |= CSP_TRAJ_NOT_SPD_BIT;
+                R *wk = ws + (int64_t)(k - 1) * E * a.B;
+#pragma unroll
+                for (int r = 0; r < N; ++r) {
+#pragma unroll
+                    for (int c = 0; c < N; ++c) { W[r][c] = Bm[r][c]; wk[(int64_t)(r * N + c) * a.B] = W[r][c]; }
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) { z[r][c] = Bm[r][N + c]; wk[(int64_t)(N * N + r * 6 + c) * a.B] = z[r][c]; }
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax) dend[r][ax] = dnext[r][ax];
+                }
+                left = right;
+                Tn = Tnn;
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) {
+                    Pp[ax] = Pc[ax]; Pc[ax] = Pn[ax]; Pn[ax] = Pnn[ax];
+#pragma unroll
+                    for (int i = 0; i < M; ++i) pbn[ax][i] = pbnn[ax][i];
+                }
+            }
+        }
+
+        // ---- back substitution: x and lambda per waypoint, then per segment T_bar and the fixed-slot gradients ----
+        R xn[N][3], ln[N][3];
+#pragma unroll
+        for (int r = 0; r < N; ++r)
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) { xn[r][ax] = xS[r][ax]; ln[r][ax] = R(0); }
+        R nanacc = R(0);
+        R carry[3] = {R(0), R(0), R(0)};   // start-of-segment part of waypoint k+1's gradient (segment k+1)
+        R Tk = R(tm[S - 1]), P0[3], P1[3], wz[E], pb[3][M];
+        vload3<IO, R>(wp + 3 * (S - 1), P0);
+        vload3<IO, R>(wp + 3 * S, P1);
+        load_rec<O, IO, R>(gco + (int64_t)(S - 1) * 3 * M, pb);
+        if (S > 1) {
+            const R *wk = ws + (int64_t)(S - 2) * E * a.B;
+#pragma unroll
+            for (int e = 0; e < E; ++e) wz[e] = wk[(int64_t)e * a.B];
+        }
+        for (int k = S - 1; k >= 0; --k) {
+            R Tp = R(1), Pm[3] = {R(0), R(0), R(0)}, wzp[E], pbp[3][M];
+            if (k >= 1) {  // prefetch segment k-1: time, start waypoint, p_bar and factors
+                Tp = R(tm[k - 1]);
+                vload3<IO, R>(wp + 3 * (k - 1), Pm);
+                load_rec<O, IO, R>(gco + (int64_t)(k - 1) * 3 * M, pbp);
+                if (k >= 2) {
+                    const R *wk = ws + (int64_t)(k - 2) * E * a.B;
+#pragma unroll
+                    for (int e = 0; e < E; ++e) wzp[e] = wk[(int64_t)e * a.B];
+                }
+            }
+            R xk[N][3], lk[N][3];
+#pragma unroll
+            for (int r = 0; r < N; ++r)
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) {
+                    if (k == 0) { xk[r][ax] = x0[r][ax]; lk[r][ax] = R(0); continue; }
+                    R v = wz[N * N + r * 6 + ax], u = wz[N * N + r * 6 + 3 + ax];
+#pragma unroll
+                    for (int c = 0; c < N; ++c) {
+                        v = fma_<R>(-wz[r * N + c], xn[c][ax], v);
+                        u = fma_<R>(-wz[r * N + c], ln[c][ax], u);
+                    }
+                    xk[r][ax] = v;
+                    lk[r][ax] = u;
+                }
+            R tp[O], ip[M];
+            powers<O, R>(Tk, tp, ip);
+            R tsum = R(0), gs[3], ge[3];
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                R d[M], c[M], db[M], lt[M];
+                d[0] = P0[ax];
+                d[O] = P1[ax];
+                lt[0] = R(0);
+                lt[O] = R(0);
+#pragma unroll
+                for (int r = 0; r < N; ++r) {
+                    d[r + 1] = xk[r][ax]; d[O + r + 1] = xn[r][ax];
+                    lt[r + 1] = lk[r][ax]; lt[O + r + 1] = ln[r][ax];
+                }
+                recover_axis<O, R>(d, tp, ip, c);
+                dbar_axis<O, 0, M, R>(pb[ax], tp, ip, db);
+                // (Qt lambda~) at the fixed slots: both positions, and the bc slots of the first / last segment.
+                // lambda~ is zero at every fixed slot, so the +w diagonal never enters.
+                R q[M];
+#pragma unroll
+                for (int aa = 0; aa < M; ++aa) {
+                    R v = R(0);
+#pragma unroll
+                    for (int bb = 0; bb < M; ++bb) {
+                        if (bb % O == 0) continue;
+                        v = fma_<R>(R(Tab<O>::QT(aa, bb)) * ip[M - 1 - aa % O - bb % O], lt[bb], v);
+                    }
+                    q[aa] = v;
+                }
+                R t = R(0);
+#pragma unroll
+                for (int aa = 0; aa < M; ++aa) {
+                    t = fma_<R>(R(aa % O) * d[aa], db[aa], t);
+                    t = fma_<R>(-R(M - 1 - aa) * c[aa], pb[ax][aa], t);
+                }
+                // sum_ab (1-2o+deriv_a+deriv_b) lambda~_a Qt_ab d_b over the free slots a
+#pragma unroll
+                for (int aa = 0; aa < M; ++aa) {
+                    if (aa % O == 0) continue;
+                    R v = R(0);
+#pragma unroll
+                    for (int bb = 0; bb < M; ++bb)
+                        v = fma_<R>(R(1 - 2 * O + aa % O + bb % O) * R(Tab<O>::QT(aa, bb)) * ip[M - 1 - aa % O - bb % O], d[bb], v);
+                    t = fma_<R>(-lt[aa], v, t);
+                }
+                tsum += t;
+                gs[ax] = db[0] - q[0];
+                ge[ax] = db[O] - q[O];
+                if (k == 0) {
+                    gbc[0][ax] = db[1] - q[1];                  // start velocity
+                    if (N >= 2) gbc[2][ax] = db[2] - q[2];      // start acceleration
+                }
+                if (k == S - 1) {
+                    gbc[1][ax] = db[O + 1] - q[O + 1];          // end velocity
+                    if (N >= 2) gbc[3][ax] = db[O + 2] - q[O + 2];
+                }
+            }
+            if (gtm) {
+                const R g = tsum * ip[1];
+                gtm[k] = IO(g);
+                nanacc = fma_<R>(R(IO(g)), R(0), nanacc);
+            }
+            if (gwp) {
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) {
+                    const IO g = IO(carry[ax] + ge[ax]);
+                    gwp[3 * (k + 1) + ax] = g;
+                    nanacc = fma_<R>(R(g), R(0), nanacc);
+                }
+            }
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) carry[ax] = gs[ax];
+#pragma unroll
+            for (int r = 0; r < N; ++r)
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) { xn[r][ax] = xk[r][ax]; ln[r][ax] = lk[r][ax]; }
+            Tk = Tp;
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                P1[ax] = P0[ax]; P0[ax] = Pm[ax];
+#pragma unroll
+                for (int i = 0; i < M; ++i) pb[ax][i] = pbp[ax][i];
+            }
+#pragma unroll
+            for (int e = 0; e < E; ++e) wz[e] = wzp[e];
+        }
+        if (gwp) {
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                const IO g = IO(carry[ax]);
+                gwp[ax] = g;
+                nanacc = fma_<R>(R(g), R(0), nanacc);
+            }
+        }
+        if (a.grad_bc) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int ax = 0; ax < 3; ++ax) nanacc = fma_<R>(gbc[r][ax], R(0), nanacc);
+            if (a.bc_per_traj) {
+                IO *gb = (IO *)a.grad_bc + b * 12;
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax) gb[r * 3 + ax] = IO(gbc[r][ax]);
+            }
+        }
+        if (!(nanacc == R(0))) status |= CSP_TRAJ_NONFINITE_BIT;
+    }
+    if (b < a.B && a.status) a.status[b] = status;
+    // shared bc: this workgroup's sum in a fixed order (the whole wave takes part, idle lanes add zeros)
+    if (a.grad_bc && !a.bc_per_traj) {
+        R *part = (R *)a.bc_part;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                const double s = wave_sum((double)gbc[r][ax]);
+                if (threadIdx.x == 0) part[(int64_t)(r * 3 + ax) * gridDim.x + blockIdx.x] = R(s);
+            }
+    }
+}
+
+// Second pass of the shared-bc reduction: one wave sums the per-workgroup partials of each of the 12 entries in a
+// fixed order (strided per lane, then an in-wave tree).
+template <typename IO, typename R>
+__global__ void __launch_bounds__(64) minsnap_vjp_bc_reduce(const R *part, int64_t nblk, IO *grad_bc) {
+    for (int e = 0; e < 12; ++e) {
+        double s = 0.0;
+        for (int64_t i = threadIdx.x; i < nblk; i += 64) s += (double)part[(int64_t)e * nblk + i];
+        s = wave_sum(s);
+        if (threadIdx.x == 0) grad_bc[e] = IO(s);
+    }
+}
+
+template <int O, typename IO> static hipError_t launch_vjp_o(const VjpArgs &a, hipStream_t st) {
+    const int64_t blocks = vjp_blocks(a.B);
+    hipLaunchKernelGGL((minsnap_vjp_kernel<O, IO, double>), dim3((unsigned)blocks), dim3(64), 0, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !a.grad_bc || a.bc_per_traj) return e;
+    hipLaunchKernelGGL((minsnap_vjp_bc_reduce<IO, double>), dim3(1), dim3(64), 0, st, (const double *)a.bc_part, blocks,
+                       (IO *)a.grad_bc);
+    return hipGetLastError();
+}
+
+template <typename IO> static hipError_t launch_vjp_r(const VjpArgs &a, hipStream_t st) {
+    switch (a.order) {
+        case 2: return launch_vjp_o<2, IO>(a, st);
+        case 3: return launch_vjp_o<3, IO>(a, st);
+        case 4: return launch_vjp_o<4, IO>(a, st);
+        case 5: return launch_vjp_o<5, IO>(a, st);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_vjp(const VjpArgs &a, bool f32, hipStream_t st) {
+    if (a.B == 0) return hipSuccess;
+    return f32 ? launch_vjp_r<float>(a, st) : launch_vjp_r<double>(a, st);
+}
+
+}  // namespace csp

@@ -123,6 +123,35 @@ int csp_minsnap_solve_batch(const csp_minsnap_desc *desc, const void *waypoints,
 /* Device scratch bytes the call above needs for `desc` (0 when the fixed-size kernel serves it). */
 size_t csp_minsnap_workspace_bytes(const csp_minsnap_desc *desc);
 
+/* Reverse mode of csp_minsnap_solve_batch: the vector-Jacobian product.  Given grad_coeffs = dL/dcoeffs, writes
+ * dL/dwaypoints, dL/dtimes and dL/dbc.  The primal is re-solved from waypoints / times / bc in the
+ * same block-LDL^T sweep that solves the adjoint system (the forward's coefficients are not read), one lane per
+ * trajectory, the factors in `workspace`.  Results are deterministic run to run (no atomics).
+ *   desc          : as for csp_minsnap_solve_batch; orders 2..5, uniform or ragged, CSP_DTYPE_F64 or CSP_DTYPE_F32
+ *                   (fp32 storage, fp64 arithmetic), vel_zero_weight(_per_traj).  CSP_ERR_UNSUPPORTED for
+ *                   path_weight != 0, order 1, CSP_FLAG_SEGMENT_MAJOR and CSP_FLAG_F32_ARITH.  Gradients with respect
+ *                   to the weights are not computed.
+ *   grad_coeffs   : [B][S][3][2*order] (trajectory-major, the layout of `coeffs`); 16-byte aligned (fp64) / 8-byte (fp32)
+ *   grad_waypoints: optional out, the layout of `waypoints`
+ *   grad_times    : optional out, the layout of `times`
+ *   grad_bc       : optional out, the shape of `bc`: [B][4][3] per trajectory, or [1][4][3] summed over the batch
+ *                   (in a fixed order).  Rows the order does not use (acceleration at order 2) are zero.
+ *   status        : optional [B] i32: CSP_TRAJ_NOT_SPD (a pivot <= 0), CSP_TRAJ_NONFINITE (a gradient this trajectory
+ *                   writes is inf/NaN)
+ *   workspace     : device scratch of csp_minsnap_vjp_workspace_bytes(desc) bytes (CSP_MEM_DEVICE, 8-byte aligned);
+ *                   may be NULL/0 with CSP_MEM_HOST.  With o = order, Smax = num_segments (uniform) or max_segments
+ *                   (ragged):
+ *                     round_up_256((Smax - 1) * ((o-1)^2 + 6(o-1)) * B * 8)
+ *                       + (bc_per_trajectory ? 0 : 12 * ceil(B / 64) * 8)
+ * CSP_MEM_HOST: staged through the cached arena, synchronous.  CSP_MEM_DEVICE: asynchronous on `hip_stream`. */
+int csp_minsnap_solve_batch_vjp(const csp_minsnap_desc *desc, const void *waypoints, const void *times,
+                                const void *bc, const void *grad_coeffs, void *grad_waypoints,
+                                void *grad_times, void *grad_bc, int32_t *status,
+                                void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Device scratch bytes csp_minsnap_solve_batch_vjp needs for `desc` (formula above; 0 for an invalid or unsupported
+ * descriptor). */
+size_t csp_minsnap_vjp_workspace_bytes(const csp_minsnap_desc *desc);
+
 /* The same solve spread over `ngpu` devices of this node from ONE process (the reference planner
  * is a single C++ process).  Trajectories are independent
  * (minimum_snap.cpp has no cross-trajectory term), so the batch is cut into `ngpu` contiguous shards, shard g on the
