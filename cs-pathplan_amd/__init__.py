@@ -37,10 +37,14 @@ FLAG_F32_ARITH = 0x8
 FLAG_LONG_SEGMENTS = 0x10
 FLAG_SPAN = 0x20
 TRAJ_OK, TRAJ_NONFINITE, TRAJ_NOT_SPD, TRAJ_SKIPPED = 0, 1, 2, 4
+TRAJ_NOT_CONVERGED = 8
+TIMEOPT_FIXED_TOTAL, TIMEOPT_TIME_PENALTY = 0, 1
 
 EXPORTED_SYMBOLS = (
     "csp_minsnap_solve_batch", "csp_minsnap_solve_batch_sharded", "csp_minsnap_workspace_bytes", "csp_minsnap_time_alloc_batch",
     "csp_minsnap_solve_batch_vjp", "csp_minsnap_vjp_workspace_bytes",
+    "csp_minsnap_cost_batch", "csp_minsnap_cost_workspace_bytes", "csp_minsnap_optimize_times_batch",
+    "csp_minsnap_timeopt_workspace_bytes",
     "csp_minsnap_solve_mixed", "csp_minsnap_mixed_workspace_bytes", "csp_minsnap_solve_multi",
     "csp_minsnap_plan_batch", "csp_minsnap_plan_workspace_bytes", "csp_minsnap_sample_batch",
     "csp_minsnap_generate_batch", "csp_minsnap_sample_capacity",
@@ -73,6 +77,27 @@ class Desc(ctypes.Structure):
     ]
 
 
+class TimeOptParams(ctypes.Structure):
+    """Mirror of `csp_minsnap_timeopt_params` (include/csp_minsnap.h)."""
+    _fields_ = [
+        ("abi_version", ctypes.c_uint32), ("mode", ctypes.c_uint32),
+        ("time_weight", ctypes.c_double), ("min_time", ctypes.c_double), ("tol", ctypes.c_double),
+        ("max_iters", ctypes.c_int32), ("reserved", ctypes.c_uint32),
+    ]
+
+
+def make_timeopt_params(mode=TIMEOPT_FIXED_TOTAL, time_weight=0.0, min_time=0.01, tol=1e-6, max_iters=100):
+    p = TimeOptParams()
+    p.abi_version = ABI_VERSION
+    p.mode = int(mode)
+    p.time_weight = float(time_weight)
+    p.min_time = float(min_time)
+    p.tol = float(tol)
+    p.max_iters = int(max_iters)
+    p.reserved = 0
+    return p
+
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         "cs-pathplan_amd: %s is missing.  Build the HIP extension first "
@@ -85,6 +110,15 @@ _lib.csp_minsnap_solve_batch_vjp.restype = ctypes.c_int
 _lib.csp_minsnap_solve_batch_vjp.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 9 + [ctypes.c_size_t, ctypes.c_void_p]
 _lib.csp_minsnap_vjp_workspace_bytes.restype = ctypes.c_size_t
 _lib.csp_minsnap_vjp_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
+_lib.csp_minsnap_cost_batch.restype = ctypes.c_int
+_lib.csp_minsnap_cost_batch.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]
+_lib.csp_minsnap_cost_workspace_bytes.restype = ctypes.c_size_t
+_lib.csp_minsnap_cost_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
+_lib.csp_minsnap_optimize_times_batch.restype = ctypes.c_int
+_lib.csp_minsnap_optimize_times_batch.argtypes = ([ctypes.POINTER(Desc), ctypes.POINTER(TimeOptParams)] + [ctypes.c_void_p] * 9
+                                                  + [ctypes.c_size_t, ctypes.c_void_p])
+_lib.csp_minsnap_timeopt_workspace_bytes.restype = ctypes.c_size_t
+_lib.csp_minsnap_timeopt_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
 _lib.csp_minsnap_solve_batch_sharded.restype = ctypes.c_int
 _lib.csp_minsnap_solve_batch_sharded.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 6 + [ctypes.c_int]
 _lib.csp_minsnap_workspace_bytes.restype = ctypes.c_size_t
@@ -478,6 +512,154 @@ def solve_batch_autograd(waypoints, times, bc=None, order=4, vel_zero_weight=0.0
         _autograd_fn = _make_autograd_fn()
     return _autograd_fn.apply(waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments,
                               vel_zero_weight_per_traj)
+
+
+def cost_workspace_bytes(desc):
+    return int(_lib.csp_minsnap_cost_workspace_bytes(ctypes.byref(desc)))
+
+
+def timeopt_workspace_bytes(desc):
+    return int(_lib.csp_minsnap_timeopt_workspace_bytes(ctypes.byref(desc)))
+
+
+class _CallInputs:
+    """waypoints / times / bc / seg_offsets / per-trajectory weights of one call, made contiguous in the memory space
+    they came in (numpy -> CSP_MEM_HOST, torch CUDA -> CSP_MEM_DEVICE), with the descriptor and an allocator for outputs."""
+
+    def __init__(self, waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj):
+        self.torch = _is_torch(waypoints)
+        ragged = seg_offsets is not None
+        if self.torch:
+            import torch
+            if not waypoints.is_cuda:
+                raise ValueError("torch inputs must be CUDA tensors (use numpy arrays for host memory)")
+            tdt = waypoints.dtype
+            self.dtype = DTYPE_F32 if tdt == torch.float32 else DTYPE_F64
+            self.dev = dev = waypoints.device
+            self.waypoints, self.times = waypoints.contiguous(), times.to(tdt).contiguous()
+            if ragged:
+                seg_offsets = seg_offsets.to(device=dev, dtype=torch.int64).contiguous()
+                B, S = seg_offsets.numel() - 1, 0
+                if max_segments is None:
+                    max_segments = int((seg_offsets[1:] - seg_offsets[:-1]).max().item()) if B else 1
+            else:
+                B, S = self.times.shape
+            bc = torch.zeros((1, 4, 3), dtype=tdt, device=dev) if bc is None else bc.to(tdt).contiguous().reshape(-1, 4, 3)
+            vwp = None
+            if vel_zero_weight_per_traj is not None:
+                vwp = vel_zero_weight_per_traj.to(device=dev, dtype=torch.float64).contiguous()
+            self.ptr = lambda t: t.data_ptr() if t is not None else None
+            mem, dev_id = MEM_DEVICE, dev.index if dev.index is not None else -1
+        else:
+            waypoints = np.asarray(waypoints)
+            self.dtype = DTYPE_F32 if waypoints.dtype == np.float32 else DTYPE_F64
+            npdt = _np_dtype(self.dtype)
+            self.waypoints = np.ascontiguousarray(waypoints, dtype=npdt)
+            self.times = np.ascontiguousarray(times, dtype=npdt)
+            if ragged:
+                seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.int64)
+                B, S = seg_offsets.shape[0] - 1, 0
+                if max_segments is None:
+                    max_segments = int(np.max(np.diff(seg_offsets))) if B else 1
+            else:
+                B, S = self.times.shape
+            bc = np.zeros((1, 4, 3), dtype=npdt) if bc is None else np.ascontiguousarray(bc, dtype=npdt).reshape(-1, 4, 3)
+            vwp = None
+            if vel_zero_weight_per_traj is not None:
+                vwp = np.ascontiguousarray(vel_zero_weight_per_traj, dtype=np.float64)
+            self.ptr = lambda a: a.ctypes.data if a is not None else None
+            mem, dev_id = MEM_HOST, -1
+        if bc.shape[0] not in (1, B):
+            raise ValueError("bc must be [4,3], [1,4,3] or [B,4,3]")
+        self.bc, self.B, self.seg_offsets, self.vwp = bc, B, seg_offsets, vwp
+        self.desc = make_desc(order, B, S, self.dtype, 0.0, vel_zero_weight, mem, bc.shape[0] == B,
+                              self.ptr(seg_offsets) if ragged else None, max_segments or 0, self.ptr(vwp), dev_id, 0)
+
+    def empty(self, shape, kind):
+        """kind: 'io' (the storage dtype), 'f64' or 'i32'."""
+        if self.torch:
+            import torch
+            dt = {"io": self.waypoints.dtype, "f64": torch.float64, "i32": torch.int32}[kind]
+            return torch.empty(shape, dtype=dt, device=self.dev)
+        dt = {"io": _np_dtype(self.dtype), "f64": np.float64, "i32": np.int32}[kind]
+        return np.empty(shape, dtype=dt)
+
+    def workspace(self, need, workspace):
+        if not self.torch or not need:
+            return None, 0
+        import torch
+        if workspace is None or workspace.numel() * workspace.element_size() < need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        return workspace.data_ptr(), need
+
+    def stream(self, stream):
+        if not self.torch:
+            return None
+        import torch
+        return ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(self.dev).cuda_stream)
+
+
+class CostResult:
+    """snap_cost_batch: cost [B] f64, grad_times (layout of times, or None), status [B] i32."""
+    __slots__ = ("cost", "grad_times", "status")
+
+    def __init__(self, cost, grad_times, status):
+        self.cost, self.grad_times, self.status = cost, grad_times, status
+
+
+def snap_cost_batch(waypoints, times, bc=None, order=4, vel_zero_weight=0.0, seg_offsets=None, max_segments=None,
+                    vel_zero_weight_per_traj=None, want_grad=True, workspace=None, stream=None):
+    """The cost J the solve minimises at `times` and its gradient dJ/dtimes (csp_minsnap_cost_batch).
+    Inputs as in solve_batch without the path penalty: numpy arrays -> host memory, torch CUDA tensors -> device memory
+    (asynchronous on the current stream)."""
+    ci = _CallInputs(waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    cost = ci.empty((ci.B,), "f64")
+    grad = ci.empty(tuple(ci.times.shape), "io") if want_grad else None
+    stt = ci.empty((ci.B,), "i32")
+    wsp, need = ci.workspace(cost_workspace_bytes(ci.desc), workspace)
+    p = ci.ptr
+    _check(_lib.csp_minsnap_cost_batch(ctypes.byref(ci.desc), p(ci.waypoints), p(ci.times), p(ci.bc), p(cost), p(grad), p(stt),
+                                       wsp, need, ci.stream(stream)))
+    return CostResult(cost, grad, stt)
+
+
+class TimeOptResult:
+    """optimize_times_batch: times (layout of the input), coeffs (or None), objective [B,2] f64 (initial, final),
+    iterations [B] i32, status [B] i32."""
+    __slots__ = ("times", "coeffs", "objective", "iterations", "status")
+
+    def __init__(self, times, coeffs, objective, iterations, status):
+        self.times, self.coeffs, self.objective, self.iterations, self.status = times, coeffs, objective, iterations, status
+
+
+_TIMEOPT_MODES = {"fixed_total": TIMEOPT_FIXED_TOTAL, "time_penalty": TIMEOPT_TIME_PENALTY}
+
+
+def optimize_times_batch(waypoints, times, bc=None, order=4, mode="fixed_total", time_weight=0.0, min_time=0.01, tol=1e-6,
+                         max_iters=100, want_coeffs=True, vel_zero_weight=0.0, seg_offsets=None, max_segments=None,
+                         vel_zero_weight_per_traj=None, workspace=None, stream=None):
+    """Segment times that minimise the snap cost (csp_minsnap_optimize_times_batch), per trajectory in one
+    launch.  mode "fixed_total": minimise J with sum(T) kept; "time_penalty": minimise J + time_weight * sum(T).
+    T >= min_time throughout.  Stops when the scaled projected-gradient measure is <= tol, or after max_iters accepted
+    iterations (status TRAJ_NOT_CONVERGED).  coeffs, when wanted, are solve_batch's at the returned times (bit-equal).
+    Inputs as in snap_cost_batch."""
+    if mode not in _TIMEOPT_MODES:
+        raise ValueError("mode: one of %r" % (tuple(_TIMEOPT_MODES),))
+    ci = _CallInputs(waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    prm = make_timeopt_params(_TIMEOPT_MODES[mode], time_weight, min_time, tol, max_iters)
+    tout = ci.empty(tuple(ci.times.shape), "io")
+    total = int(ci.times.numel() if ci.torch else ci.times.size)
+    co = ci.empty((total, 3, 2 * int(order)) if ci.seg_offsets is not None else (ci.B, ci.times.shape[1], 3, 2 * int(order)),
+                  "io") if want_coeffs else None
+    obj = ci.empty((ci.B, 2), "f64")
+    its = ci.empty((ci.B,), "i32")
+    stt = ci.empty((ci.B,), "i32")
+    wsp, need = ci.workspace(timeopt_workspace_bytes(ci.desc), workspace)
+    p = ci.ptr
+    _check(_lib.csp_minsnap_optimize_times_batch(ctypes.byref(ci.desc), ctypes.byref(prm), p(ci.waypoints), p(ci.times),
+                                                 p(ci.bc), p(tout), p(co), p(obj), p(its), p(stt), wsp, need,
+                                                 ci.stream(stream)))
+    return TimeOptResult(tout, co, obj, its, stt)
 
 
 class PreparedMulti:

@@ -1358,3 +1358,198 @@ int csp_minsnap_solve_batch_vjp(const csp_minsnap_desc *desc, const void *waypoi
 }
 
 }  // extern "C"
+
+namespace {
+
+// csp_minsnap_cost_batch / csp_minsnap_optimize_times_batch: the VJP's scope (validate_vjp).
+size_t cost_ws_bytes(const Shape &s) {
+    return align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::timeopt_ws_entries(s.order) * (size_t)s.B * 8, 256);
+}
+
+size_t timeopt_ws_bytes(const Shape &s, size_t *vec_off) {
+    const size_t factors = cost_ws_bytes(s);
+    if (vec_off) *vec_off = factors;
+    return factors + 4 * (size_t)s.Smax * (size_t)s.B * 8;
+}
+
+int validate_timeopt(const csp_minsnap_desc *d, const csp_minsnap_timeopt_params *p, Shape &s) {
+    int rc = validate_vjp(d, s);
+    if (rc != CSP_OK) return rc;
+    if (!p || p->abi_version != CSP_MINSNAP_ABI_VERSION) return CSP_ERR_INVALID_ARG;
+    if (p->mode != CSP_TIMEOPT_FIXED_TOTAL && p->mode != CSP_TIMEOPT_TIME_PENALTY) return CSP_ERR_INVALID_ARG;
+    if (p->mode == CSP_TIMEOPT_TIME_PENALTY && !(p->time_weight > 0.0 && std::isfinite(p->time_weight))) return CSP_ERR_INVALID_ARG;
+    if (!(p->min_time > 0.0 && std::isfinite(p->min_time))) return CSP_ERR_INVALID_ARG;
+    if (!(p->tol >= 0.0) || p->max_iters < 0) return CSP_ERR_INVALID_ARG;
+    return CSP_OK;
+}
+
+// FIXED_TOTAL needs sum_j T_j >= S * min_time for every trajectory: checked on the host when the times are host memory.
+bool totals_feasible(const Shape &s, const int64_t *seg_off, const void *times, double tmin) {
+    for (int64_t b = 0; b < s.B; ++b) {
+        const int64_t s0 = s.ragged ? seg_off[b] : b * (int64_t)s.S, s1 = s.ragged ? seg_off[b + 1] : s0 + s.S;
+        double c = 0.0;
+        for (int64_t j = s0; j < s1; ++j) c += s.f32 ? (double)((const float *)times)[j] : ((const double *)times)[j];
+        if (c < (double)(s1 - s0) * tmin) return false;
+    }
+    return true;
+}
+
+void timeopt_args(const csp_minsnap_desc *d, const Shape &s, csp::TimeOptArgs &a) {
+    a = csp::TimeOptArgs{};
+    a.vel_zero_weight = d->vel_zero_weight;
+    a.B = s.B; a.S = s.S; a.Smax = s.Smax; a.order = s.order; a.bc_per_traj = d->bc_per_trajectory ? 1 : 0;
+}
+
+int dispatch_cost(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const void *bc, double *cost,
+                  void *grad, int32_t *status, const int64_t *seg_off, const double *vw_per, void *ws, size_t ws_size,
+                  hipStream_t st) {
+    const size_t need = cost_ws_bytes(s);
+    if (need > 0 && (!ws || ws_size < need)) return CSP_ERR_WORKSPACE;
+    if ((uintptr_t)ws & 7u) return CSP_ERR_WORKSPACE;
+    csp::TimeOptArgs a;
+    timeopt_args(d, s, a);
+    a.wp = wp; a.times = tm; a.bc = bc; a.cost = cost; a.grad = grad; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.ws = ws; a.vw_per = vw_per;
+    hipError_t e = csp::launch_cost(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, "cost kernel launch");
+    return CSP_OK;
+}
+
+int dispatch_timeopt(const csp_minsnap_desc *d, const csp_minsnap_timeopt_params *p, const Shape &s, const void *wp,
+                     const void *tm, const void *bc, void *tout, void *co, double *obj, int32_t *iters, int32_t *status,
+                     const int64_t *seg_off, const double *vw_per, void *ws, size_t ws_size, hipStream_t st) {
+    size_t vec_off = 0;
+    const size_t need = timeopt_ws_bytes(s, &vec_off);
+    if (!ws || ws_size < need || ((uintptr_t)ws & 7u)) return CSP_ERR_WORKSPACE;
+    csp::TimeOptArgs a;
+    timeopt_args(d, s, a);
+    a.wp = wp; a.times = tm; a.bc = bc; a.times_out = tout; a.objective = obj; a.iterations = iters; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.ws = ws; a.vec = (double *)((char *)ws + vec_off); a.vw_per = vw_per;
+    a.mode = p->mode == CSP_TIMEOPT_FIXED_TOTAL ? csp::CSP_TIMEOPT_FIXED_TOTAL_V : csp::CSP_TIMEOPT_TIME_PENALTY_V;
+    a.time_weight = p->time_weight; a.min_time = p->min_time; a.tol = p->tol; a.max_iters = p->max_iters;
+    hipError_t e = csp::launch_timeopt(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, "time optimiser launch");
+    if (!co) return CSP_OK;
+    // the coefficients are csp_minsnap_solve_batch's at the optimised times; its workspace (0 or the generic kernel's
+    // factors, the same size as ours) is the factor region
+    return dispatch(d, s, wp, tout, bc, co, nullptr, nullptr, seg_off, vw_per, ws, vec_off, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t csp_minsnap_cost_workspace_bytes(const csp_minsnap_desc *desc) {
+    Shape s;
+    if (validate_vjp(desc, s) != CSP_OK) return 0;
+    return cost_ws_bytes(s);
+}
+
+size_t csp_minsnap_timeopt_workspace_bytes(const csp_minsnap_desc *desc) {
+    Shape s;
+    if (validate_vjp(desc, s) != CSP_OK) return 0;
+    return timeopt_ws_bytes(s, nullptr);
+}
+
+int csp_minsnap_cost_batch(const csp_minsnap_desc *desc, const void *waypoints, const void *times, const void *bc,
+                           double *cost, void *grad_times, int32_t *status, void *workspace, size_t workspace_bytes,
+                           void *hip_stream) {
+    Shape s;
+    int rc = validate_vjp(desc, s);
+    if (rc != CSP_OK) return rc;
+    if (s.B == 0) return CSP_OK;
+    if (!waypoints || !times || !bc || !cost) return CSP_ERR_INVALID_ARG;
+    rc = select_device(desc->device_id);
+    if (rc != CSP_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+
+    if (desc->mem_space == CSP_MEM_DEVICE)
+        return dispatch_cost(desc, s, waypoints, times, bc, cost, grad_times, status, desc->seg_offsets,
+                             desc->vel_zero_weight_per_traj, workspace, workspace_bytes, st);
+
+    int64_t total_seg;
+    if (s.ragged) {
+        total_seg = desc->seg_offsets[s.B];
+        for (int64_t b = 0; b < s.B; ++b) {
+            const int64_t n = desc->seg_offsets[b + 1] - desc->seg_offsets[b];
+            if (n < 0 || n > s.Smax) return CSP_ERR_INVALID_ARG;
+        }
+    } else {
+        total_seg = s.B * (int64_t)s.S;
+    }
+    const size_t n_wp = (size_t)(total_seg + s.B) * 3 * s.elt, n_tm = (size_t)total_seg * s.elt;
+    const size_t n_bc = (size_t)(desc->bc_per_trajectory ? s.B : 1) * 12 * s.elt;
+    const size_t n_ws = cost_ws_bytes(s);
+    csp::HostCall hc(current_device(), st);
+    const size_t o_wp = hc.in(waypoints, n_wp), o_tm = hc.in(times, n_tm), o_bc = hc.in(bc, n_bc);
+    const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
+    const size_t o_vw = desc->vel_zero_weight_per_traj ? hc.in(desc->vel_zero_weight_per_traj, (size_t)s.B * 8) : 0;
+    const size_t o_c = hc.out(cost, (size_t)s.B * 8);
+    const size_t o_g = grad_times ? hc.out(grad_times, n_tm) : 0;
+    const size_t o_st = status ? hc.out(status, (size_t)s.B * 4) : 0;
+    const size_t o_ws = hc.scratch(n_ws);
+    CSP_HIP(hc.upload());
+    rc = dispatch_cost(desc, s, hc.ptr(o_wp), hc.ptr(o_tm), hc.ptr(o_bc), hc.ptr<double>(o_c),
+                       grad_times ? hc.ptr(o_g) : nullptr, status ? hc.ptr<int32_t>(o_st) : nullptr,
+                       s.ragged ? hc.ptr<const int64_t>(o_so) : nullptr,
+                       desc->vel_zero_weight_per_traj ? hc.ptr<const double>(o_vw) : nullptr, hc.ptr(o_ws), n_ws, st);
+    if (rc != CSP_OK) return rc;
+    CSP_HIP(hc.download());
+    return CSP_OK;
+}
+
+int csp_minsnap_optimize_times_batch(const csp_minsnap_desc *desc, const csp_minsnap_timeopt_params *prm,
+                                     const void *waypoints, const void *times_in, const void *bc, void *times_out,
+                                     void *coeffs, double *objective, int32_t *iterations, int32_t *status,
+                                     void *workspace, size_t workspace_bytes, void *hip_stream) {
+    Shape s;
+    int rc = validate_timeopt(desc, prm, s);
+    if (rc != CSP_OK) return rc;
+    if (s.B == 0) return CSP_OK;
+    if (!waypoints || !times_in || !bc || !times_out) return CSP_ERR_INVALID_ARG;
+    if (desc->mem_space == CSP_MEM_HOST) {
+        if (s.ragged)
+            for (int64_t b = 0; b < s.B; ++b) {
+                const int64_t n = desc->seg_offsets[b + 1] - desc->seg_offsets[b];
+                if (n < 0 || n > s.Smax) return CSP_ERR_INVALID_ARG;
+            }
+        if (prm->mode == CSP_TIMEOPT_FIXED_TOTAL && !totals_feasible(s, desc->seg_offsets, times_in, prm->min_time))
+            return CSP_ERR_INVALID_ARG;
+    }
+    rc = select_device(desc->device_id);
+    if (rc != CSP_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+
+    if (desc->mem_space == CSP_MEM_DEVICE)
+        return dispatch_timeopt(desc, prm, s, waypoints, times_in, bc, times_out, coeffs, objective, iterations, status,
+                                desc->seg_offsets, desc->vel_zero_weight_per_traj, workspace, workspace_bytes, st);
+
+    const int64_t total_seg = s.ragged ? desc->seg_offsets[s.B] : s.B * (int64_t)s.S;
+    const size_t m = 2 * (size_t)s.order;
+    const size_t n_wp = (size_t)(total_seg + s.B) * 3 * s.elt, n_tm = (size_t)total_seg * s.elt;
+    const size_t n_bc = (size_t)(desc->bc_per_trajectory ? s.B : 1) * 12 * s.elt;
+    const size_t n_co = (size_t)total_seg * 3 * m * s.elt;
+    const size_t n_ws = timeopt_ws_bytes(s, nullptr);
+    csp::HostCall hc(current_device(), st);
+    const size_t o_wp = hc.in(waypoints, n_wp), o_tm = hc.in(times_in, n_tm), o_bc = hc.in(bc, n_bc);
+    const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
+    const size_t o_vw = desc->vel_zero_weight_per_traj ? hc.in(desc->vel_zero_weight_per_traj, (size_t)s.B * 8) : 0;
+    const size_t o_to = hc.out(times_out, n_tm);
+    const size_t o_co = coeffs ? hc.out(coeffs, n_co) : 0;
+    const size_t o_ob = objective ? hc.out(objective, (size_t)s.B * 16) : 0;
+    const size_t o_it = iterations ? hc.out(iterations, (size_t)s.B * 4) : 0;
+    const size_t o_st = status ? hc.out(status, (size_t)s.B * 4) : 0;
+    const size_t o_ws = hc.scratch(n_ws);
+    CSP_HIP(hc.upload());
+    rc = dispatch_timeopt(desc, prm, s, hc.ptr(o_wp), hc.ptr(o_tm), hc.ptr(o_bc), hc.ptr(o_to), coeffs ? hc.ptr(o_co) : nullptr,
+                          objective ? hc.ptr<double>(o_ob) : nullptr, iterations ? hc.ptr<int32_t>(o_it) : nullptr,
+                          status ? hc.ptr<int32_t>(o_st) : nullptr, s.ragged ? hc.ptr<const int64_t>(o_so) : nullptr,
+                          desc->vel_zero_weight_per_traj ? hc.ptr<const double>(o_vw) : nullptr, hc.ptr(o_ws), n_ws, st);
+    if (rc != CSP_OK) return rc;
+    CSP_HIP(hc.download());
+    return CSP_OK;
+}
+
+}  // extern "C"

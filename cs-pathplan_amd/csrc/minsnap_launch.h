@@ -107,6 +107,36 @@ inline int64_t vjp_blocks(int64_t B) { return (B + 63) / 64; }
 inline size_t vjp_ws_entries(int order) { const int n = order - 1; return (size_t)(n * n + 6 * n); }
 hipError_t launch_vjp(const VjpArgs &a, bool f32, hipStream_t st);
 
+// Snap cost, its time gradient and the segment-time optimiser (minsnap_timeopt.hip): scope as the VJP.  One lane per
+// trajectory, workgroups of 64.
+constexpr int CSP_TRAJ_NOT_CONVERGED_BIT = 8;                        // include/csp_minsnap.h CSP_TRAJ_NOT_CONVERGED
+constexpr int CSP_TIMEOPT_FIXED_TOTAL_V = 0, CSP_TIMEOPT_TIME_PENALTY_V = 1;   // CSP_TIMEOPT_* modes
+struct TimeOptArgs {
+    const void *wp, *times, *bc;   // as GenericArgs; `times` = the input times
+    void *times_out;               // optimiser: [B][S] (the layout of times)
+    double *cost;                  // cost kernel: [B]
+    void *grad;                    // cost kernel: dJ/dtimes in the layout of times, or null
+    double *objective;             // optimiser: [B][2] initial, final objective, or null
+    int32_t *iterations;           // optimiser: [B] or null
+    int32_t *status;               // [B] or null
+    const int64_t *seg_off;        // ragged prefix sums or null
+    void *ws;                      // f64 [(Smax-1)][(o-1)^2 + 3(o-1)][B] block-LDL^T factors
+    double *vec;                   // optimiser: f64 [4][Smax][B] current / trial times and their gradients
+    const double *vw_per;          // [B] or null
+    double vel_zero_weight;
+    double time_weight, min_time, tol;
+    int64_t B;
+    int S;                         // uniform S (ignored when seg_off != null)
+    int Smax;
+    int order;
+    int bc_per_traj;
+    int mode;
+    int max_iters;
+};
+inline size_t timeopt_ws_entries(int order) { const int n = order - 1; return (size_t)(n * n + 3 * n); }
+hipError_t launch_cost(const TimeOptArgs &a, bool f32, hipStream_t st);
+hipError_t launch_timeopt(const TimeOptArgs &a, bool f32, hipStream_t st);
+
 struct TimeAllocArgs {
     const void *wp;
     void *times;

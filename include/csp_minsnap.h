@@ -86,6 +86,8 @@ enum { CSP_MEM_HOST = 0, CSP_MEM_DEVICE = 1 };
 #define CSP_TRAJ_NOT_SPD 2     /* a pivot of the free-derivative Hessian R_PP was <= 0              */
 #define CSP_TRAJ_SKIPPED 4     /* csp_minsnap_solve_mixed only: the trajectory was NOT solved (its order is outside 2..5
                                   or its segment count outside 1..min(256, max_segments)); its coefficient block is left untouched (zero-filled with CSP_MEM_HOST) */
+#define CSP_TRAJ_NOT_CONVERGED 8 /* csp_minsnap_optimize_times_batch only: the stopping rule was not met (max_iters reached, or
+                                  no decrease within rounding); the times returned are the last accepted ones          */
 
 typedef struct csp_minsnap_desc {
     uint32_t abi_version;       /* CSP_MINSNAP_ABI_VERSION                                       */
@@ -151,6 +153,76 @@ int csp_minsnap_solve_batch_vjp(const csp_minsnap_desc *desc, const void *waypoi
 /* Device scratch bytes csp_minsnap_solve_batch_vjp needs for `desc` (formula above; 0 for an invalid or unsupported
  * descriptor). */
 size_t csp_minsnap_vjp_workspace_bytes(const csp_minsnap_desc *desc);
+
+/* The cost the solve minimises and its gradient with respect to the segment times:
+ *   J(T)    = sum_axes sum_j [ integral_0^T_j (p_j^(order))^2 dt + w (v_j(0)^2 + v_j(T_j)^2) ]   at the solve's optimum
+ *   dJ/dT_j = (1/T_j) sum_axes sum_ab (deriv_a + deriv_b + 1 - 2 order) Qt_ab(T_j) d_a d_b   (envelope theorem: the
+ *             optimum's endpoint derivatives d are held fixed, no adjoint solve; the w term does not depend on T)
+ * One lane per trajectory: the solve's block-LDL^T sweep and back substitution, no coefficients.
+ *   desc       : the scope of csp_minsnap_solve_batch_vjp (orders 2..5, uniform or ragged, fp64 storage or fp32 storage
+ *                with fp64 arithmetic, shared or per-trajectory bc and vel_zero_weight).  CSP_ERR_UNSUPPORTED for
+ *                path_weight != 0, order 1, CSP_FLAG_SEGMENT_MAJOR and CSP_FLAG_F32_ARITH.
+ *   cost       : out, [B] f64
+ *   grad_times : optional out, the layout and storage type of `times`
+ *   status     : optional [B] i32: CSP_TRAJ_NOT_SPD, CSP_TRAJ_NONFINITE (J or a gradient is inf/NaN)
+ *   workspace  : device scratch of csp_minsnap_cost_workspace_bytes(desc) bytes (CSP_MEM_DEVICE, 8-byte aligned); may be
+ *                NULL/0 with CSP_MEM_HOST.  With o = order, Smax = num_segments (uniform) or max_segments (ragged):
+ *                  round_up_256((Smax - 1) * ((o-1)^2 + 3(o-1)) * B * 8)
+ * CSP_MEM_HOST: staged through the cached arena, synchronous.  CSP_MEM_DEVICE: asynchronous on `hip_stream`. */
+int csp_minsnap_cost_batch(const csp_minsnap_desc *desc, const void *waypoints, const void *times, const void *bc,
+                           double *cost, void *grad_times, int32_t *status, void *workspace, size_t workspace_bytes,
+                           void *hip_stream);
+/* Device scratch bytes csp_minsnap_cost_batch needs (formula above; 0 for an invalid or unsupported descriptor). */
+size_t csp_minsnap_cost_workspace_bytes(const csp_minsnap_desc *desc);
+
+/* segment-time optimisation modes */
+#define CSP_TIMEOPT_FIXED_TOTAL 0u  /* minimise J subject to sum_j T_j = sum_j T_j^in, T_j >= min_time */
+#define CSP_TIMEOPT_TIME_PENALTY 1u /* minimise J + time_weight * sum_j T_j, T_j >= min_time          */
+
+typedef struct csp_minsnap_timeopt_params {
+    uint32_t abi_version;       /* CSP_MINSNAP_ABI_VERSION                                          */
+    uint32_t mode;              /* CSP_TIMEOPT_FIXED_TOTAL | CSP_TIMEOPT_TIME_PENALTY                */
+    double time_weight;         /* rho > 0, CSP_TIMEOPT_TIME_PENALTY only                           */
+    double min_time;            /* t_min > 0                                                        */
+    double tol;                 /* >= 0: stop when max_j |x_j - P(x_j - g_j)| <= tol (scaled, below)  */
+    int32_t max_iters;          /* >= 0 accepted iterations at most                                 */
+    uint32_t reserved;
+} csp_minsnap_timeopt_params;
+
+/* Segment-time optimisation: per trajectory, the times that minimise the snap cost J (fixed total) or J + rho sum T
+ * (time penalty), starting from times_in, in ONE launch.  Spectral projected gradient: Barzilai-Borwein
+ * steps with monotone Armijo backtracking, in the scaled variables x = T / mean(T_start) and objective / its initial value,
+ * with an exact projection (Michelot's algorithm for the fixed total, a clip for the time penalty).  The start is
+ * times_in, projected onto the feasible set when an entry is below min_time.  Every evaluation is a full pass of
+ * csp_minsnap_cost_batch's kernel (the trial's gradient is the next iteration's).
+ *   Stopping rule: max_j |x_j - P(x_j - g^_j)| <= tol, g^ the scaled gradient; otherwise CSP_TRAJ_NOT_CONVERGED after
+ *   max_iters accepted iterations (max_iters = 0 returns the start).  The objective never increases: final <= initial
+ *   bit for bit from the kernel's own evaluations.  The bounds hold exactly; the fixed total holds to 1e-12 relative
+ *   (with fp32 storage, to the rounding of the returned times).  Lanes of a wave take different numbers of iterations
+ *   and the wave runs until its slowest lane is done.
+ *   desc        : the scope of csp_minsnap_cost_batch (same CSP_ERR_UNSUPPORTED cases)
+ *   prm         : CSP_ERR_INVALID_ARG for NULL, a bad abi_version or mode, time_weight <= 0 with the time penalty,
+ *                 min_time <= 0, tol < 0, max_iters < 0, and (CSP_MEM_HOST) sum_j T_j^in < S * min_time with the fixed
+ *                 total.  With CSP_MEM_DEVICE the last check is per trajectory on the device: such a trajectory is
+ *                 returned unchanged with CSP_TRAJ_NOT_CONVERGED, iterations 0 and NaN objectives.
+ *   times_out   : out, the layout of times_in
+ *   coeffs      : optional out, csp_minsnap_solve_batch(times_out) -- computed by that call's own dispatch, so bit-equal
+ *                 to a separate solve
+ *   objective   : optional out, [B][2] f64: initial (at the start) and final objective (J, plus rho sum T)
+ *   iterations  : optional out, [B] i32 accepted iterations
+ *   status      : optional out, [B] i32: CSP_TRAJ_NOT_SPD / CSP_TRAJ_NONFINITE (the trajectory stops at its last
+ *                 accepted times), CSP_TRAJ_NOT_CONVERGED
+ *   workspace   : device scratch of csp_minsnap_timeopt_workspace_bytes(desc) bytes (CSP_MEM_DEVICE, 8-byte aligned);
+ *                 may be NULL/0 with CSP_MEM_HOST:
+ *                   round_up_256((Smax - 1) * ((o-1)^2 + 3(o-1)) * B * 8) + 4 * Smax * B * 8
+ * CSP_MEM_HOST: staged through the cached arena, synchronous.  CSP_MEM_DEVICE: asynchronous on `hip_stream`. */
+int csp_minsnap_optimize_times_batch(const csp_minsnap_desc *desc, const csp_minsnap_timeopt_params *prm,
+                                     const void *waypoints, const void *times_in, const void *bc, void *times_out,
+                                     void *coeffs, double *objective, int32_t *iterations, int32_t *status,
+                                     void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Device scratch bytes csp_minsnap_optimize_times_batch needs (formula above; 0 for an invalid or unsupported
+ * descriptor). */
+size_t csp_minsnap_timeopt_workspace_bytes(const csp_minsnap_desc *desc);
 
 /* The same solve spread over `ngpu` devices of this node from ONE process (the reference planner
  * is a single C++ process).  Trajectories are independent
