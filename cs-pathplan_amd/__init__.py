@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "csp_minsnap_solve_batch_vjp", "csp_minsnap_vjp_workspace_bytes",
     "csp_minsnap_cost_batch", "csp_minsnap_cost_workspace_bytes", "csp_minsnap_optimize_times_batch",
     "csp_minsnap_timeopt_workspace_bytes",
+    "csp_minsnap_solve_periodic_batch", "csp_minsnap_periodic_workspace_bytes",
     "csp_minsnap_solve_mixed", "csp_minsnap_mixed_workspace_bytes", "csp_minsnap_solve_multi",
     "csp_minsnap_plan_batch", "csp_minsnap_plan_workspace_bytes", "csp_minsnap_sample_batch",
     "csp_minsnap_generate_batch", "csp_minsnap_sample_capacity",
@@ -119,6 +120,10 @@ _lib.csp_minsnap_optimize_times_batch.argtypes = ([ctypes.POINTER(Desc), ctypes.
                                                   + [ctypes.c_size_t, ctypes.c_void_p])
 _lib.csp_minsnap_timeopt_workspace_bytes.restype = ctypes.c_size_t
 _lib.csp_minsnap_timeopt_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
+_lib.csp_minsnap_solve_periodic_batch.restype = ctypes.c_int
+_lib.csp_minsnap_solve_periodic_batch.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]
+_lib.csp_minsnap_periodic_workspace_bytes.restype = ctypes.c_size_t
+_lib.csp_minsnap_periodic_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
 _lib.csp_minsnap_solve_batch_sharded.restype = ctypes.c_int
 _lib.csp_minsnap_solve_batch_sharded.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 6 + [ctypes.c_int]
 _lib.csp_minsnap_workspace_bytes.restype = ctypes.c_size_t
@@ -660,6 +665,75 @@ def optimize_times_batch(waypoints, times, bc=None, order=4, mode="fixed_total",
                                                  p(ci.bc), p(tout), p(co), p(obj), p(its), p(stt), wsp, need,
                                                  ci.stream(stream)))
     return TimeOptResult(tout, co, obj, its, stt)
+
+
+def periodic_workspace_bytes(desc):
+    return int(_lib.csp_minsnap_periodic_workspace_bytes(ctypes.byref(desc)))
+
+
+class PeriodicResult:
+    """solve_periodic_batch: coeffs ([B,S,3,2o], or [sum S_b,3,2o] ragged), cost [B] f64 (or None), grad_times (layout
+    of times, or None), status [B] i32."""
+    __slots__ = ("coeffs", "cost", "grad_times", "status")
+
+    def __init__(self, coeffs, cost, grad_times, status):
+        self.coeffs, self.cost, self.grad_times, self.status = coeffs, cost, grad_times, status
+
+
+def solve_periodic_batch(waypoints, times, order=4, vel_zero_weight=0.0, seg_offsets=None, max_segments=None,
+                         vel_zero_weight_per_traj=None, want_cost=False, want_grad=False, workspace=None, stream=None):
+    """The periodic (closed-loop) minimum-snap solve (csp_minsnap_solve_periodic_batch): segment j runs
+    from waypoint j to waypoint (j+1) mod S, every knot is interior and there is no bc.  waypoints [B,S,3] (no repeated
+    closing point), times [B,S]; ragged: waypoints [sum S_b,3] and times [sum S_b], both split by seg_offsets [B+1].
+    numpy arrays -> host memory, torch CUDA tensors -> device memory (asynchronous on the current stream).  want_cost /
+    want_grad add the snap cost J and dJ/dtimes; the coefficients are the same bits either way."""
+    ci = _CallInputs(waypoints, times, None, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    m = 2 * int(order)
+    total = int(ci.times.numel() if ci.torch else ci.times.size)
+    co = ci.empty((total, 3, m) if ci.seg_offsets is not None else (ci.B, ci.times.shape[1], 3, m), "io")
+    cost = ci.empty((ci.B,), "f64") if want_cost else None
+    grad = ci.empty(tuple(ci.times.shape), "io") if want_grad else None
+    stt = ci.empty((ci.B,), "i32")
+    wsp, need = ci.workspace(periodic_workspace_bytes(ci.desc), workspace)
+    p = ci.ptr
+    _check(_lib.csp_minsnap_solve_periodic_batch(ctypes.byref(ci.desc), p(ci.waypoints), p(ci.times), p(co), p(cost),
+                                                 p(grad), p(stt), wsp, need, ci.stream(stream)))
+    return PeriodicResult(co, cost, grad, stt)
+
+
+def periodic_time_alloc_batch(waypoints, v_avg, min_time_s, seg_offsets=None):
+    """Segment times of closed loops by the reference's rule T = max(|dP|/v_avg, min_time_s) (time_alloc_batch), the
+    closing segment P_{S-1} -> P_0 included.  waypoints [B,S,3] -> times [B,S]; ragged: waypoints [sum S_b,3] split by
+    seg_offsets [B+1] -> times [sum S_b].  numpy arrays or torch CUDA tensors."""
+    is_t = _is_torch(waypoints)
+    if seg_offsets is None:
+        if is_t:
+            import torch
+            closed = torch.cat([waypoints, waypoints[:, :1]], dim=1)
+        else:
+            waypoints = np.asarray(waypoints)
+            closed = np.concatenate([waypoints, waypoints[:, :1]], axis=1)
+        return time_alloc_batch(closed, v_avg, min_time_s)
+    # ragged: the open-chain layout puts S_b + 1 points per trajectory; an empty loop gets one (unused) zero point
+    off = np.asarray(seg_offsets.cpu() if _is_torch(seg_offsets) else seg_offsets, dtype=np.int64)
+    B = off.shape[0] - 1
+    total = int(off[-1]) if B >= 0 else 0
+    lens = np.diff(off)
+    idx = np.empty(total + B, dtype=np.int64)
+    dst = off[:-1] + np.arange(B)
+    pos = np.arange(total) + np.repeat(np.arange(B), lens)
+    idx[pos] = np.arange(total)
+    idx[dst + lens] = np.where(lens > 0, off[:-1], total)
+    if is_t:
+        import torch
+        src = torch.cat([waypoints.reshape(-1, 3), waypoints.new_zeros((1, 3))])
+        closed = src[torch.from_numpy(idx).to(waypoints.device)]
+        so = torch.from_numpy(off).to(waypoints.device)
+    else:
+        waypoints = np.asarray(waypoints)
+        src = np.concatenate([waypoints.reshape(-1, 3), np.zeros((1, 3), dtype=waypoints.dtype)])
+        closed, so = src[idx], off
+    return time_alloc_batch(closed, v_avg, min_time_s, seg_offsets=so)
 
 
 class PreparedMulti:

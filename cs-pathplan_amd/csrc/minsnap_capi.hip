@@ -1553,3 +1553,85 @@ int csp_minsnap_optimize_times_batch(const csp_minsnap_desc *desc, const csp_min
 }
 
 }  // extern "C"
+
+namespace {
+
+// csp_minsnap_solve_periodic_batch: the VJP's scope (validate_vjp); bc_per_trajectory is ignored (there is no bc).
+size_t periodic_ws_bytes(const Shape &s) {
+    return align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::periodic_ws_entries(s.order) * (size_t)s.B * 8, 256);
+}
+
+int dispatch_periodic(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, void *co, double *cost,
+                      void *grad, int32_t *status, const int64_t *seg_off, const double *vw_per, void *ws, hipStream_t st) {
+    csp::PeriodicArgs a{};
+    a.wp = wp; a.times = tm; a.coeffs = co; a.cost = cost; a.grad = grad; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.ws = ws; a.vw_per = vw_per;
+    a.vel_zero_weight = d->vel_zero_weight;
+    a.B = s.B; a.S = s.S; a.order = s.order;
+    hipError_t e = csp::launch_periodic(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, "periodic kernel launch");
+    return CSP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t csp_minsnap_periodic_workspace_bytes(const csp_minsnap_desc *desc) {
+    Shape s;
+    if (validate_vjp(desc, s) != CSP_OK) return 0;
+    return periodic_ws_bytes(s);
+}
+
+int csp_minsnap_solve_periodic_batch(const csp_minsnap_desc *desc, const void *waypoints, const void *times, void *coeffs,
+                                     double *cost, void *grad_times, int32_t *status, void *workspace,
+                                     size_t workspace_bytes, void *hip_stream) {
+    Shape s;
+    int rc = validate_vjp(desc, s);
+    if (rc != CSP_OK) return rc;
+    if (s.B == 0) return CSP_OK;
+    if (!waypoints || !times || !coeffs) return CSP_ERR_INVALID_ARG;
+    const size_t n_ws = periodic_ws_bytes(s);
+    if (desc->mem_space == CSP_MEM_DEVICE) {
+        if (n_ws > 0 && (!workspace || workspace_bytes < n_ws)) return CSP_ERR_WORKSPACE;
+        if ((uintptr_t)workspace & 7u) return CSP_ERR_WORKSPACE;
+        if ((uintptr_t)coeffs & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // records are stored as 2-element vectors
+    } else if (s.ragged) {
+        for (int64_t b = 0; b < s.B; ++b) {
+            const int64_t n = desc->seg_offsets[b + 1] - desc->seg_offsets[b];
+            if (n < 0 || n > s.Smax) return CSP_ERR_INVALID_ARG;
+        }
+    }
+    rc = select_device(desc->device_id);
+    if (rc != CSP_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+
+    if (desc->mem_space == CSP_MEM_DEVICE)
+        return dispatch_periodic(desc, s, waypoints, times, coeffs, cost, grad_times, status, desc->seg_offsets,
+                                 desc->vel_zero_weight_per_traj, workspace, st);
+
+    const int64_t total_seg = s.ragged ? desc->seg_offsets[s.B] : s.B * (int64_t)s.S;
+    const size_t m = 2 * (size_t)s.order;
+    const size_t n_wp = (size_t)total_seg * 3 * s.elt, n_tm = (size_t)total_seg * s.elt;
+    const size_t n_co = (size_t)total_seg * 3 * m * s.elt;
+    csp::HostCall hc(current_device(), st);
+    const size_t o_wp = hc.in(waypoints, n_wp), o_tm = hc.in(times, n_tm);
+    const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
+    const size_t o_vw = desc->vel_zero_weight_per_traj ? hc.in(desc->vel_zero_weight_per_traj, (size_t)s.B * 8) : 0;
+    const size_t o_co = hc.out(coeffs, n_co);
+    const size_t o_c = cost ? hc.out(cost, (size_t)s.B * 8) : 0;
+    const size_t o_g = grad_times ? hc.out(grad_times, n_tm) : 0;
+    const size_t o_st = status ? hc.out(status, (size_t)s.B * 4) : 0;
+    const size_t o_ws = hc.scratch(n_ws);
+    CSP_HIP(hc.upload());
+    rc = dispatch_periodic(desc, s, hc.ptr(o_wp), hc.ptr(o_tm), hc.ptr(o_co), cost ? hc.ptr<double>(o_c) : nullptr,
+                           grad_times ? hc.ptr(o_g) : nullptr, status ? hc.ptr<int32_t>(o_st) : nullptr,
+                           s.ragged ? hc.ptr<const int64_t>(o_so) : nullptr,
+                           desc->vel_zero_weight_per_traj ? hc.ptr<const double>(o_vw) : nullptr, hc.ptr(o_ws), st);
+    if (rc != CSP_OK) return rc;
+    CSP_HIP(hc.download());
+    return CSP_OK;
+}
+
+}  // extern "C"

@@ -137,6 +137,27 @@ inline size_t timeopt_ws_entries(int order) { const int n = order - 1; return (s
 hipError_t launch_cost(const TimeOptArgs &a, bool f32, hipStream_t st);
 hipError_t launch_timeopt(const TimeOptArgs &a, bool f32, hipStream_t st);
 
+// Periodic (closed-loop) solve (minsnap_periodic.hip): orders 2..5, uniform or ragged, f64 storage or f32 storage with
+// f64 arithmetic, zero-velocity penalty.  One lane per trajectory, workgroups of 64.  Trajectory b owns waypoints AND
+// times seg0 .. seg0+S_b-1 (no closing waypoint).  Cost and gradient are computed when `cost` or `grad` is non-null.
+struct PeriodicArgs {
+    const void *wp;                // [B][S][3] (or ragged concatenation)
+    const void *times;             // [B][S]
+    void *coeffs;                  // [B][S][3][2o]
+    double *cost;                  // [B] or null
+    void *grad;                    // dJ/dtimes in the layout of times, or null
+    int32_t *status;               // [B] or null
+    const int64_t *seg_off;        // ragged prefix sums or null
+    void *ws;                      // f64 [(Smax-1)][2(o-1)^2 + 3(o-1)][B]: W, V, z per knot 1..S-1
+    const double *vw_per;          // [B] or null
+    double vel_zero_weight;
+    int64_t B;
+    int S;                         // uniform S (ignored when seg_off != null)
+    int order;
+};
+inline size_t periodic_ws_entries(int order) { const int n = order - 1; return (size_t)(2 * n * n + 3 * n); }
+hipError_t launch_periodic(const PeriodicArgs &a, bool f32, hipStream_t st);
+
 struct TimeAllocArgs {
     const void *wp;
     void *times;

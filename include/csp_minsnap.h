@@ -224,6 +224,37 @@ int csp_minsnap_optimize_times_batch(const csp_minsnap_desc *desc, const csp_min
  * descriptor). */
 size_t csp_minsnap_timeopt_workspace_bytes(const csp_minsnap_desc *desc);
 
+/* The periodic (closed-loop) minimum-snap solve: S >= 1 segments around a loop, segment j from
+ * waypoint P_j to P_{(j+1) mod S} in time T_j.  Every knot is interior, the wrap P_{S-1} -> P_0 included: derivatives
+ * 1..order-1 are continuous around the whole loop, and there are no boundary conditions.  One lane per trajectory, a
+ * bordered block-LDL^T sweep (knot 0 is the border), the factors in `workspace`.  Results are deterministic run to run.
+ *   desc       : the scope of csp_minsnap_solve_batch_vjp (orders 2..5, uniform or ragged, CSP_DTYPE_F64 or CSP_DTYPE_F32
+ *                with fp64 arithmetic, vel_zero_weight scalar or per trajectory).  CSP_ERR_UNSUPPORTED for order 1 or
+ *                6+, path_weight != 0, CSP_FLAG_SEGMENT_MAJOR and CSP_FLAG_F32_ARITH.  bc_per_trajectory is ignored.
+ *   waypoints  : [B][S][3], the S distinct loop points (no repeated closing point)
+ *   times      : [B][S]
+ *   RAGGED LAYOUT (num_segments == 0): trajectory b owns waypoints AND times seg_offsets[b] .. seg_offsets[b+1]-1, i.e.
+ *                waypoints is [seg_offsets[B]][3].  This differs from the open chain, whose waypoints are offset by +b.
+ *                A trajectory with S_b = 0 gets cost 0 and status 0; nothing else is written for it.
+ *   coeffs     : out, [B][S][3][2*order], the record format of csp_minsnap_solve_batch; 16-byte aligned (fp64) / 8-byte
+ *                (fp32).  Bit-identical whether or not cost / grad_times are requested.
+ *   cost       : optional out, [B] f64: the snap cost J of csp_minsnap_cost_batch (w term included) at the solution
+ *   grad_times : optional out, dJ/dT_j by the envelope theorem, the layout and storage type of `times`
+ *   status     : optional out, [B] i32: CSP_TRAJ_NOT_SPD (a pivot <= 0, the border's Schur complement included: only
+ *                non-positive or non-finite times cause it), CSP_TRAJ_NONFINITE (a stored coefficient, J or a gradient
+ *                is inf/NaN)
+ *   workspace  : device scratch of csp_minsnap_periodic_workspace_bytes(desc) bytes (CSP_MEM_DEVICE, 8-byte aligned);
+ *                may be NULL/0 with CSP_MEM_HOST.  With o = order, Smax = num_segments (uniform) or max_segments (ragged):
+ *                  round_up_256((Smax - 1) * (2(o-1)^2 + 3(o-1)) * B * 8)
+ * Arguments are checked before a device is looked for.
+ * CSP_MEM_HOST: staged through the cached arena, synchronous.  CSP_MEM_DEVICE: asynchronous on `hip_stream`. */
+int csp_minsnap_solve_periodic_batch(const csp_minsnap_desc *desc, const void *waypoints, const void *times, void *coeffs,
+                                     double *cost, void *grad_times, int32_t *status, void *workspace,
+                                     size_t workspace_bytes, void *hip_stream);
+/* Device scratch bytes csp_minsnap_solve_periodic_batch needs (formula above; 0 for an invalid or unsupported
+ * descriptor). */
+size_t csp_minsnap_periodic_workspace_bytes(const csp_minsnap_desc *desc);
+
 /* The same solve spread over `ngpu` devices of this node from ONE process (the reference planner
  * is a single C++ process).  Trajectories are independent
  * (minimum_snap.cpp has no cross-trajectory term), so the batch is cut into `ngpu` contiguous shards, shard g on the
