@@ -16,12 +16,14 @@ namespace csp {
 hipError_t launch_fixed_o2(const GenericArgs &a, int cus, hipStream_t st);
 hipError_t launch_fixed_o3(const GenericArgs &a, int cus, hipStream_t st);
 hipError_t launch_fixed_o4a(const GenericArgs &a, int cus, hipStream_t st);   // S = 2..9
-hipError_t launch_fixed_o4b(const GenericArgs &a, int cus, hipStream_t st);   // S = 10..16
+hipError_t launch_fixed_o4b(const GenericArgs &a, int cus, hipStream_t st);   // S = 14..16
+hipError_t launch_fixed_o4c(const GenericArgs &a, int cus, hipStream_t st);   // S = 10..13
 hipError_t launch_fixed_o5(const GenericArgs &a, int cus, hipStream_t st);
 hipError_t launch_fixedpath_o2(const GenericArgs &a, hipStream_t st);
 hipError_t launch_fixedpath_o3(const GenericArgs &a, hipStream_t st);
 hipError_t launch_fixedpath_o4a(const GenericArgs &a, hipStream_t st);  // S = 2..9
-hipError_t launch_fixedpath_o4b(const GenericArgs &a, hipStream_t st);  // S = 10..16
+hipError_t launch_fixedpath_o4b(const GenericArgs &a, hipStream_t st);  // S = 14..16
+hipError_t launch_fixedpath_o4c(const GenericArgs &a, hipStream_t st);  // S = 10..13
 
 bool fixed_supported(int order, int S, bool f32, double path_weight, bool ragged, bool seg_major) {
     if (f32 || ragged || S < 2) return false;
@@ -47,7 +49,7 @@ hipError_t launch_fixed(const GenericArgs &a, hipStream_t st) {
         switch (a.order) {
             case 2: return launch_fixedpath_o2(a, st);
             case 3: return launch_fixedpath_o3(a, st);
-            case 4: return a.S <= 9 ? launch_fixedpath_o4a(a, st) : launch_fixedpath_o4b(a, st);
+            case 4: return a.S <= 9 ? launch_fixedpath_o4a(a, st) : a.S <= 13 ? launch_fixedpath_o4c(a, st) : launch_fixedpath_o4b(a, st);
         }
         return hipErrorInvalidValue;
     }
@@ -67,7 +69,7 @@ hipError_t launch_fixed(const GenericArgs &a, hipStream_t st) {
     switch (a.order) {
         case 2: return launch_fixed_o2(a, cus, st);
         case 3: return launch_fixed_o3(a, cus, st);
-        case 4: return a.S <= 9 ? launch_fixed_o4a(a, cus, st) : launch_fixed_o4b(a, cus, st);
+        case 4: return a.S <= 9 ? launch_fixed_o4a(a, cus, st) : a.S <= 13 ? launch_fixed_o4c(a, cus, st) : launch_fixed_o4b(a, cus, st);
         case 5: return launch_fixed_o5(a, cus, st);
     }
     return hipErrorInvalidValue;

@@ -51,17 +51,40 @@ namespace fixedk {
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() would also wait for every
 // outstanding global store (vmcnt(0)); the persistent kernel keeps stores and the next
 // slice's LDS-DMA in flight across its barriers.
-// 16-byte coefficient store.  `nt` (wave-uniform, GenericArgs::nt_stores): non-temporal, for batches whose coefficients
-// exceed the Infinity Cache -- B = 524288: 348 us against 378 us (67.9 % against 62.5 % of HBM peak); at B = 65536, whose
-// 201 MB the cache absorbs, the ordinary store is the faster one (42.5 us against 46.1 us), so the launcher decides.
+// 16-byte coefficient store.  NT: non-temporal, for batches whose coefficients exceed the Infinity Cache -- B = 524288:
+// 348 us against 378 us (67.9 % against 62.5 % of HBM peak); at B = 65536, whose 201 MB the cache absorbs, the ordinary
+// store is the faster one (42.5 us against 46.1 us), so the launcher decides (nt_stores_for) and picks the instantiation.
+// The flavour is a template parameter: as a run-time select every store was a pair of branches around both flavours,
+// which cut the bursts into two-instruction basic blocks.
 typedef double v2d_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void store16(char *p, const double2 &v, bool nt) {
-    if (nt) {
+template <bool NT> __device__ __forceinline__ void store16(char *p, const double2 &v) {
+    if constexpr (NT) {
         v2d_t x = {v.x, v.y};
         __builtin_nontemporal_store(x, reinterpret_cast<v2d_t *>(p));
     } else {
         *reinterpret_cast<double2 *>(p) = v;
     }
+}
+// A burst's 32-bit lane byte offset, re-materialised in the burst's own basic block.  Hoisted out of the slice loop
+// as a 64-bit zero-extended pair, the offset no longer matches the scalar-base store form (instruction selection works
+// per block), so the unpredicated bursts fetch it through this once, ahead of their LDS reads.
+__device__ __forceinline__ unsigned burst_off(unsigned voff) {
+    asm volatile("" : "+v"(voff));
+    return voff;
+}
+// store16 at (wave-uniform base) + (32-bit lane byte offset from burst_off), for the unpredicated bursts: the shape the
+// scalar-base form of the global store expresses (base in an SGPR pair, offset in one VGPR), so a burst carries no
+// per-store 64-bit vector address arithmetic.  `ubase` MUST be wave-uniform: it is pinned in scalar registers.
+template <bool NT> __device__ __forceinline__ void store16u(char *ubase, unsigned voff, const double2 &v) {
+    typedef __attribute__((address_space(1))) v2d_t *gptr_t;
+    // The empty statement pins the base (displacement included) in a scalar register pair: left to itself hipcc
+    // re-associates the sum to (base + lane offset) + displacement and carries a 64-bit vector address per store.
+    unsigned long long u = reinterpret_cast<unsigned long long>(ubase);
+    asm("" : "+s"(u));
+    gptr_t p = reinterpret_cast<gptr_t>(u + voff);
+    const v2d_t x = {v.x, v.y};
+    if constexpr (NT) __builtin_nontemporal_store(x, p);
+    else *p = x;
 }
 
 __device__ __forceinline__ void lds_barrier() {
@@ -214,11 +237,12 @@ template <int O, int S, bool BOTTOM> struct LineRing {
     __device__ static __forceinline__ constexpr int pos(int x) { return (x % G::RINGB) / 8; }
     // Stores the lines completed by record g (already in the ring).  tbase: the slice's first trajectory in coeffs
     // (wave-uniform).  PRED: rows may be dead (ragged slice, skip mask): bit i of live8 = row i*8 + lane/8 is stored.
-    template <bool PRED>
-    __device__ static __forceinline__ void flush(int g, const double *stage, char *tbase, int lane, bool nt, unsigned live8) {
+    template <bool PRED, bool NT>
+    __device__ static __forceinline__ void flush(int g, const double *stage, char *tbase, int lane, unsigned live8) {
         const int q = lane >> 3, p = lane & 7;
         const int l_lane = q * G::ROW + p * 2;
-        const unsigned g_lane = (unsigned)(q * RS + p * 16);
+        // the predicated form (path kernels: one branch per store) keeps plain vector addresses
+        const unsigned g_lane = PRED ? (unsigned)(q * RS + p * 16) : burst_off((unsigned)(q * RS + p * 16));
         const int rlo = g * RECB, rhi = rlo + RECB;
         // top role (written = [rlo, HI)): lines that START inside the record; bottom role (written = [LO, rhi)): lines that END inside it
         const int l0 = BOTTOM ? rlo / 128 : (rlo + 127) / 128;
@@ -234,7 +258,10 @@ template <int O, int S, bool BOTTOM> struct LineRing {
                 for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const double2 *>(stage + l_lane + pos(ell * 128) + i * 8 * G::ROW);
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
-                    if (pv && (!PRED || ((live8 >> i) & 1u))) store16(tbase + ell * 128 + (size_t)i * 8 * RS + g_lane, v[i], nt);
+                    if (pv && (!PRED || ((live8 >> i) & 1u))) {
+                        if constexpr (PRED) store16<NT>(tbase + ell * 128 + (size_t)i * 8 * RS + g_lane, v[i]);
+                        else store16u<NT>(tbase + ell * 128 + (size_t)i * 8 * RS, g_lane, v[i]);
+                    }
             }
         }
     }
@@ -315,11 +342,12 @@ template <bool BOTTOM> struct RoleBc {
 // NAX = 3: one lane per trajectory (all three axes).  NAX = 1 (small batches, see launch_s): THREE lanes per trajectory,
 // lane = (axis ax0, staging row `row`), each factorising redundantly and carrying one right-hand side -- about half the
 // instructions per lane, which is what a lone latency-bound wave is made of.
-template <int O, int S, bool BOTTOM, bool STATUS, bool FULL, bool SEGMAJ, bool STASH, class In, class Hook, int NAX = 3>
+template <int O, int S, bool BOTTOM, bool STATUS, bool FULL, bool SEGMAJ, bool STASH, bool NT, class In, class Hook, int NAX = 3>
 __device__ __forceinline__ void fixed_body(const GenericArgs &a, int64_t b0, int64_t b, int lane,
                                            const In &in, const RoleBc<BOTTOM> &rbc, double *stage, double *partner_stage,
                                            double *tst, const Hook &after_exchange, int rows = 64, int row_ = 0, int ax0 = 0) {
     static_assert(NAX == 3 || (NAX == 1 && !FULL && !STASH), "the axis-per-lane mapping serves the narrow one-slice kernel only");
+    static_assert(FULL || !NT, "only the full-slice kernels have a non-temporal flavour");
     const int row = NAX == 3 ? lane : row_;   // staging-tile row = trajectory within the slice
     constexpr int N = O - 1, M = 2 * O;
     constexpr int HS = BOTTOM ? S / 2 : (S + 1) / 2;   // segments of THIS role; both roles meet at waypoint ceil(S/2)
@@ -554,15 +582,16 @@ __device__ __forceinline__ void fixed_body(const GenericArgs &a, int64_t b0, int
         if (paired) {
             // pair base = record of the even segment; TOP meets the odd record first, BOTTOM the even one
             char *pbase = reinterpret_cast<char *>((double *)a.coeffs + (b0 * S + (g & ~1)) * L::REC);  // uniform
-            const bool nt = a.nt_stores != 0;
             if (first) {
+                const unsigned o8b = burst_off(o8);
                 double2 v[8];   // 8 rows x 128 bytes per store
 #pragma unroll
                 for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const double2 *>(stage + l8 + i * 8 * ROW);
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
-                    store16(pbase + (BOTTOM ? 0 : 256) + (size_t)i * 8 * RS + o8, v[i], nt);
+                    store16u<NT>(pbase + (BOTTOM ? 0 : 256) + (size_t)i * 8 * RS, o8b, v[i]);
             } else {
+                const unsigned o16b = burst_off(o16);
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {  // 4 rows x 256 bytes per store, two batches of 8
                     double2 v[8];
@@ -570,11 +599,11 @@ __device__ __forceinline__ void fixed_body(const GenericArgs &a, int64_t b0, int
                     for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const double2 *>(stage + l16 + (h * 8 + i) * 4 * ROW);
 #pragma unroll
                     for (int i = 0; i < 8; ++i)
-                        store16(pbase + (BOTTOM ? 128 : 0) + (size_t)(h * 8 + i) * 4 * RS + o16, v[i], nt);
+                        store16u<NT>(pbase + (BOTTOM ? 128 : 0) + (size_t)(h * 8 + i) * 4 * RS, o16b, v[i]);
                 }
             }
         } else if (RING) {
-            LR::template flush<false>(g, stage, reinterpret_cast<char *>((double *)a.coeffs + b0 * S * L::REC), lane, a.nt_stores != 0, 0xffu);
+            LR::template flush<false, NT>(g, stage, reinterpret_cast<char *>((double *)a.coeffs + b0 * S * L::REC), lane, 0xffu);
         } else {
             char *gbase = reinterpret_cast<char *>((double *)a.coeffs + (SEGMAJ ? ((int64_t)g * a.Btotal + a.Boffset + b0) : (b0 * S + g)) * L::REC);  // uniform
             if (FULL) {
@@ -582,16 +611,16 @@ __device__ __forceinline__ void fixed_body(const GenericArgs &a, int64_t b0, int
                 // off, not made to repeat a neighbour's piece (duplicates are traffic)
                 if (lane < L::RPI * L::LPR) {
                     constexpr int NFULL = 64 / L::RPI;      // stores whose RPI rows are all < 64
+                    const unsigned g_offb = burst_off(g_off);
                     double2 v[NFULL];
 #pragma unroll
                     for (int i = 0; i < NFULL; ++i)
                         v[i] = *reinterpret_cast<const double2 *>(stage + lds_off + i * L::RPI * ROW);
-                    const bool nt = a.nt_stores != 0;
 #pragma unroll
-                    for (int i = 0; i < NFULL; ++i) store16(gbase + (size_t)i * L::RPI * RS + g_off, v[i], nt);
+                    for (int i = 0; i < NFULL; ++i) store16u<NT>(gbase + (size_t)i * L::RPI * RS, g_offb, v[i]);
                     if (NFULL < L::NI && NFULL * L::RPI + grp < 64)   // the ragged last store
-                        store16(gbase + (size_t)NFULL * L::RPI * RS + g_off,
-                                *reinterpret_cast<const double2 *>(stage + lds_off + NFULL * L::RPI * ROW), nt);
+                        store16u<NT>(gbase + (size_t)NFULL * L::RPI * RS, g_offb,
+                                     *reinterpret_cast<const double2 *>(stage + lds_off + NFULL * L::RPI * ROW));
                 }
             } else {
                 // the axis-per-lane mapping serves slices of <= 16 rows: only the first stores can hold one
@@ -622,7 +651,8 @@ __device__ __forceinline__ void fixed_body(const GenericArgs &a, int64_t b0, int
 
 // FULL = every workgroup owns 64 real trajectories (B % 64 == 0); the ragged remainder of a
 // batch is a second, single-workgroup launch of the FULL=false variant.
-template <int O, int S, bool STATUS, bool FULL, bool SEGMAJ, int NAX = 3>
+// NT (FULL only): the coefficient stores are non-temporal (store16u).
+template <int O, int S, bool STATUS, bool FULL, bool SEGMAJ, int NAX = 3, bool NT = false>
 __global__ void __launch_bounds__(128) minsnap_fixed_kernel(GenericArgs a, MultiTable mt) {
     using L = FixedLds<O, S>;
     __shared__ __attribute__((aligned(16))) double lds[L::TOTAL_DOUBLES];
@@ -713,13 +743,13 @@ __global__ void __launch_bounds__(128) minsnap_fixed_kernel(GenericArgs a, Multi
         const LdsInputs<S, false> in{l_wp, l_tm, row};
         RoleBc<false> rbc;
         rbc.load(a, b);
-        fixed_body<O, S, false, STATUS, FULL, SEGMAJ, false, LdsInputs<S, false>, NoHook, NAX>(
+        fixed_body<O, S, false, STATUS, FULL, SEGMAJ, false, NT, LdsInputs<S, false>, NoHook, NAX>(
             a, b0, b, lane, in, rbc, l_stage, l_stage + L::STAGE_DOUBLES, nullptr, NoHook{}, rows, row, ax0);
     } else {
         const LdsInputs<S, true> in{l_wp, l_tm, row};
         RoleBc<true> rbc;
         rbc.load(a, b);
-        fixed_body<O, S, true, STATUS, FULL, SEGMAJ, false, LdsInputs<S, true>, NoHook, NAX>(
+        fixed_body<O, S, true, STATUS, FULL, SEGMAJ, false, NT, LdsInputs<S, true>, NoHook, NAX>(
             a, b0, b, lane, in, rbc, l_stage + L::STAGE_DOUBLES, l_stage, nullptr, NoHook{}, rows, row, ax0);
     }
 }
@@ -767,7 +797,7 @@ template <int S> struct SlicePrefetch {
     __device__ __forceinline__ void operator()() const { if (next < n_slices) issue(next); }
 };
 
-template <int O, int S, bool BOTTOM, bool STATUS, bool SEGMAJ>
+template <int O, int S, bool BOTTOM, bool STATUS, bool SEGMAJ, bool NT>
 __device__ __forceinline__ void persistent_role_loop(const GenericArgs &a, int n_slices, int lane, const double *l_wp,
                                                      const double *l_tm, double *stage, double *partner_stage,
                                                      double *tst, SlicePrefetch<S> pf) {
@@ -798,7 +828,7 @@ __device__ __forceinline__ void persistent_role_loop(const GenericArgs &a, int n
         const int64_t b0 = slice * 64;
         pf.next = slice + gridDim.x;
         // the image is dead once both waves passed the exchange barrier: prefetch the next slice there
-        fixed_body<O, S, BOTTOM, STATUS, true, SEGMAJ, true>(a, b0, b0 + lane, lane, in, rbc, stage, partner_stage, tst, pf);
+        fixed_body<O, S, BOTTOM, STATUS, true, SEGMAJ, true, NT>(a, b0, b0 + lane, lane, in, rbc, stage, partner_stage, tst, pf);
         first = false;
     }
 }
@@ -806,7 +836,7 @@ __device__ __forceinline__ void persistent_role_loop(const GenericArgs &a, int n
 // Persistent variant for the full workgroups of a batch: gridDim.x workgroups (two per CU) walk the
 // batch with stride gridDim.x; the NEXT slice's inputs stream into LDS while the current slice is
 // back-substituted and stored, so only a workgroup's very first copy-in is exposed.
-template <int O, int S, bool STATUS, bool SEGMAJ>
+template <int O, int S, bool STATUS, bool SEGMAJ, bool NT>
 __global__ void __launch_bounds__(128) minsnap_fixed_persistent_kernel(GenericArgs a, int n_slices) {
     using L = FixedLds<O, S>;
     // image (waypoints, times) | two staging tiles | two time stashes (the forward sweep parks the
@@ -831,8 +861,8 @@ __global__ void __launch_bounds__(128) minsnap_fixed_persistent_kernel(GenericAr
     CSP_STAMP(0);
     if ((int64_t)blockIdx.x < n_slices) pf.issue(blockIdx.x);
     // one loop per role: each wave's instruction stream holds a single specialisation
-    if (role == 0) persistent_role_loop<O, S, false, STATUS, SEGMAJ>(a, n_slices, lane, l_wp, l_tm, l_stage, l_stage + L::STAGE_DOUBLES, l_tst, pf);
-    else persistent_role_loop<O, S, true, STATUS, SEGMAJ>(a, n_slices, lane, l_wp, l_tm, l_stage + L::STAGE_DOUBLES, l_stage, l_tst + L::HT * 64, pf);
+    if (role == 0) persistent_role_loop<O, S, false, STATUS, SEGMAJ, NT>(a, n_slices, lane, l_wp, l_tm, l_stage, l_stage + L::STAGE_DOUBLES, l_tst, pf);
+    else persistent_role_loop<O, S, true, STATUS, SEGMAJ, NT>(a, n_slices, lane, l_wp, l_tm, l_stage + L::STAGE_DOUBLES, l_stage, l_tst + L::HT * 64, pf);
 }
 
 // ---- host side: launch one order's kernels -----------------------------------------------------
@@ -923,8 +953,14 @@ hipError_t launch_s(const GenericArgs &a, int cus, hipStream_t st) {
             // ones (round 2, B = 524288: 261 / 392 / 312 us ordinary against 499 / 841 / 404 us non-temporal).
             constexpr bool WHOLE_LINES = !SM && (O == 4 || LineGeom<O, S>::OK);
             f.nt_stores = (WHOLE_LINES || O == 4) ? nt_stores_for(a.B, S, O) : (nt_forced() == 1 ? 1 : 0);
-            if (a.persistent && !a.bc_per_traj && !a.vw_per) hipLaunchKernelGGL((minsnap_fixed_persistent_kernel<O, S, ST, SM>), dim3((unsigned)pgrid), block, 0, st, f, (int)n_full);
-            else hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, ST, true, SM>), dim3((unsigned)n_full), block, 0, st, f, MultiTable{});
+            // the store flavour is a compile-time property of the kernel: one instantiation each
+            auto full = [&](auto nt_tag) {
+                constexpr bool NT = decltype(nt_tag)::value;
+                if (a.persistent && !a.bc_per_traj && !a.vw_per) hipLaunchKernelGGL((minsnap_fixed_persistent_kernel<O, S, ST, SM, NT>), dim3((unsigned)pgrid), block, 0, st, f, (int)n_full);
+                else hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, ST, true, SM, 3, NT>), dim3((unsigned)n_full), block, 0, st, f, MultiTable{});
+            };
+            if (f.nt_stores) full(std::true_type{});
+            else full(std::false_type{});
         }
         if (rem) hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, ST, false, SM>), dim3(1), block, 0, st, t, MultiTable{});
     };

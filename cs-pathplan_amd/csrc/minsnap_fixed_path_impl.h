@@ -95,8 +95,9 @@ template <int S, bool BOTTOM> struct HalfRing {
     __device__ static __forceinline__ constexpr int pos(int x) { return (x % RINGB) / 8; }   // doubles
     // One segment's records of the slice: cn = this lane's new record (12 doubles, [axis][power]), cp = its previous one
     // (segment g+1 for the top role, g-1 for the bottom role; unused at the role's first record).
+    template <bool NT>
     __device__ static __forceinline__ void put_and_flush(int g, const double (&cn)[12], const double (&cp)[12], double *tile, char *tbase,
-                                                         int lane, bool nt, unsigned live8) {
+                                                         int lane, unsigned live8) {
         const int rlo = g * RECB, rhi = rlo + RECB;
         constexpr int C128 = 128;
         // bytes of the previous record that still wait for their line
@@ -146,7 +147,7 @@ template <int S, bool BOTTOM> struct HalfRing {
                 for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const double2 *>(tile + (i * 8 + q) * ROW + poff);
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (pv && ((live8 >> (h * 4 + i)) & 1u)) store16(tbase + ell * 128 + (size_t)(h * 32 + i * 8) * RS + g_lane, v[i], nt);
+                    if (pv && ((live8 >> (h * 4 + i)) & 1u)) store16<NT>(tbase + ell * 128 + (size_t)(h * 32 + i * 8) * RS + g_lane, v[i]);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();   // every lane has read before the other half overwrites the tile
@@ -172,8 +173,9 @@ template <int S, bool BOTTOM> struct TimeRegInputs {
     __device__ __forceinline__ double P(int j, int ax) const { return l_wp[lane * (S + 1) * 3 + (BOTTOM ? S - j : j) * 3 + ax]; }
 };
 
-// One full twisted sweep.  PEN = false: pass A (fills tau[]); PEN = true: pass B (stores, deviation).
-template <int O, int S, bool BOTTOM, bool PEN, bool STATUS, class In>
+// One full twisted sweep.  PEN = false: pass A (fills tau[]); PEN = true: pass B (stores, deviation; NT: non-temporal
+// coefficient stores, store16).
+template <int O, int S, bool BOTTOM, bool PEN, bool STATUS, bool NT, class In>
 __device__ __forceinline__ void path_sweep(const GenericArgs &a, int64_t b0, int rows, int lane, const In &in,
                                            const RoleBc<BOTTOM> &rbc, double pw, const double *l_hw, double *stage,
                                            double *xchg, double *partner_xchg, const int *l_skip,
@@ -526,12 +528,12 @@ __device__ __forceinline__ void path_sweep(const GenericArgs &a, int64_t b0, int
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             if constexpr (DRING) {
-                HalfRing<S, BOTTOM>::put_and_flush(g, cnew, cprev, stage, reinterpret_cast<char *>((double *)a.coeffs + b0 * S * L::REC), lane,
-                                                   a.nt_stores != 0, live8);
+                HalfRing<S, BOTTOM>::template put_and_flush<NT>(g, cnew, cprev, stage, reinterpret_cast<char *>((double *)a.coeffs + b0 * S * L::REC), lane,
+                                                                live8);
 #pragma unroll
                 for (int i = 0; i < 12; ++i) cprev[i] = cnew[i];
             } else if (RING) {
-                LR::template flush<true>(g, stage, reinterpret_cast<char *>((double *)a.coeffs + b0 * S * L::REC), lane, a.nt_stores != 0, live8);
+                LR::template flush<true, NT>(g, stage, reinterpret_cast<char *>((double *)a.coeffs + b0 * S * L::REC), lane, live8);
             } else {
                 char *gbase = reinterpret_cast<char *>((double *)a.coeffs + (b0 * S + g) * L::REC);
 #pragma unroll
@@ -539,7 +541,7 @@ __device__ __forceinline__ void path_sweep(const GenericArgs &a, int64_t b0, int
                     const int row = i * L::RPI + grp;
                     if (lane < L::RPI * L::LPR && row < rows && !l_skip[row]) {
                         const double2 v2 = *reinterpret_cast<const double2 *>(stage + lds_off + i * L::RPI * ROW);
-                        store16(gbase + (size_t)i * L::RPI * RS + g_off, v2, a.nt_stores != 0);
+                        store16<NT>(gbase + (size_t)i * L::RPI * RS + g_off, v2);
                     }
                 }
             }
@@ -552,7 +554,7 @@ __device__ __forceinline__ void path_sweep(const GenericArgs &a, int64_t b0, int
     }
 }
 
-template <int O, int S, bool BOTTOM, bool STATUS, bool DENSE>
+template <int O, int S, bool BOTTOM, bool STATUS, bool DENSE, bool NT>
 __device__ __forceinline__ void path_role(const GenericArgs &a, int64_t b0, int rows, int64_t b, int lane,
                                           const double *l_wp, const double *l_tm, const double *l_hw, double *stage,
                                           double *xchg, double *partner_xchg, const int *l_skip, double *l_dev, int *l_bits) {
@@ -581,7 +583,7 @@ __device__ __forceinline__ void path_role(const GenericArgs &a, int64_t b0, int 
             tau[j] = BOTTOM ? 16 - sg : sg;
         }
     } else {
-        path_sweep<O, S, BOTTOM, false, STATUS>(a, b0, rows, lane, in, rbc, a.path_weight, l_hw, stage, xchg, partner_xchg, l_skip, tau, spd, nanacc, maxdev);
+        path_sweep<O, S, BOTTOM, false, STATUS, false>(a, b0, rows, lane, in, rbc, a.path_weight, l_hw, stage, xchg, partner_xchg, l_skip, tau, spd, nanacc, maxdev);
         if (a.tau_mode == 1 && lane < rows) {
 #pragma unroll
             for (int j = 0; j < HS; ++j) a.tstar[(int64_t)(BOTTOM ? S - 1 - j : j) * a.B + b] = BOTTOM ? 16 - tau[j] : tau[j];
@@ -589,7 +591,7 @@ __device__ __forceinline__ void path_role(const GenericArgs &a, int64_t b0, int 
     }
     spd = true;  // the reported status is the penalised solve's
     CSP_STAMP(2);
-    path_sweep<O, S, BOTTOM, true, STATUS>(a, b0, rows, lane, in, rbc, a.path_weight, l_hw, stage, xchg, partner_xchg, l_skip, tau, spd, nanacc, maxdev);
+    path_sweep<O, S, BOTTOM, true, STATUS, NT>(a, b0, rows, lane, in, rbc, a.path_weight, l_hw, stage, xchg, partner_xchg, l_skip, tau, spd, nanacc, maxdev);
     // the reference's max_deviation is the maximum over ALL segments and the status covers both
     // halves: the bottom role hands its part to the top role, which writes (plain stores, and only
     // for live trajectories: a re-solve pass must leave finished trajectories untouched)
@@ -608,7 +610,7 @@ __device__ __forceinline__ void path_role(const GenericArgs &a, int64_t b0, int 
 
 // One workgroup per 64-trajectory slice (path-penalty solves are not the streaming headline: no
 // persistent/prefetch structure here).  `skip` marks trajectories the re-solve loop has finished.
-template <int O, int S, bool STATUS>
+template <int O, int S, bool STATUS, bool NT>
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(path_dense<O, S> ? 2 : 1)))
 minsnap_fixed_path_kernel(GenericArgs a) {
     using L = FixedLds<O, S>;
@@ -706,8 +708,8 @@ minsnap_fixed_path_kernel(GenericArgs a) {
     CSP_STAMP(1);
     int64_t b = b0 + lane;
     if (b >= a.B) b = a.B - 1;
-    if (role == 0) path_role<O, S, false, STATUS, DENSE>(a, b0, rows, b, lane, l_wp, l_tm, l_hw, l_stage, l_stage, l_stage + TILE, l_skip, l_dev, l_bits);
-    else path_role<O, S, true, STATUS, DENSE>(a, b0, rows, b, lane, l_wp, l_tm, l_hw, l_stage + TILE, l_stage + TILE, l_stage, l_skip, l_dev, l_bits);
+    if (role == 0) path_role<O, S, false, STATUS, DENSE, NT>(a, b0, rows, b, lane, l_wp, l_tm, l_hw, l_stage, l_stage, l_stage + TILE, l_skip, l_dev, l_bits);
+    else path_role<O, S, true, STATUS, DENSE, NT>(a, b0, rows, b, lane, l_wp, l_tm, l_hw, l_stage + TILE, l_stage + TILE, l_stage, l_skip, l_dev, l_bits);
 }
 
 template <int O, int S> hipError_t launch_path_s(const GenericArgs &a, hipStream_t st) {
@@ -735,8 +737,14 @@ template <int O, int S> hipError_t launch_path_s(const GenericArgs &a, hipStream
     // (dense order-2 variant: the four workgroups of a CU start stagger x S x 64 clocks apart; with the closed-form search of
     // round 3 -- CSP_PATH_STAGGER = 0 / 2 / 3 / 4 / 5 / 6 / 8: 33.2 / 30.6 / 30.2 / 30.3 / 30.3 / 30.8 / 32.1 us at B = 65536, S = 16)
     f.stagger = stagger_env >= 0 ? stagger_env : (path_dense<O, S> ? 4 : O == 3 ? (S + 8) / 16 : O == 4 ? (3 * S + 8) / 16 : 0);
-    if (a.status) hipLaunchKernelGGL((minsnap_fixed_path_kernel<O, S, true>), grid, block, 0, st, f);
-    else hipLaunchKernelGGL((minsnap_fixed_path_kernel<O, S, false>), grid, block, 0, st, f);
+    // the store flavour is a compile-time property of the kernel (store16): one instantiation each
+    auto go = [&](auto nt_tag) {
+        constexpr bool NT = decltype(nt_tag)::value;
+        if (a.status) hipLaunchKernelGGL((minsnap_fixed_path_kernel<O, S, true, NT>), grid, block, 0, st, f);
+        else hipLaunchKernelGGL((minsnap_fixed_path_kernel<O, S, false, NT>), grid, block, 0, st, f);
+    };
+    if (f.nt_stores) go(std::true_type{});
+    else go(std::false_type{});
     return hipGetLastError();
 }
 

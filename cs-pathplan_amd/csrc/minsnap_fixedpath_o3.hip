@@ -1,8 +1,10 @@
 // minsnap_fixedpath_o3.hip -- instantiates the register-resident path-penalty kernels
-// (minsnap_fixed_path_impl.h) for derivative order 3, S = 2..16 segments.
+// (minsnap_fixed_path_impl.h) for derivative order 3, S = 2..11 segments (12..16: minsnap_fixedpath_o3b.hip).
 #include "minsnap_fixed_path_impl.h"
 
 namespace csp {
+
+hipError_t launch_fixedpath_o3b(const GenericArgs &a, hipStream_t st);   // S = 12..16
 
 hipError_t launch_fixedpath_o3(const GenericArgs &a, hipStream_t st) {
     switch (a.S) {
@@ -16,13 +18,8 @@ hipError_t launch_fixedpath_o3(const GenericArgs &a, hipStream_t st) {
         case 9: return fixedk::launch_path_s<3, 9>(a, st);
         case 10: return fixedk::launch_path_s<3, 10>(a, st);
         case 11: return fixedk::launch_path_s<3, 11>(a, st);
-        case 12: return fixedk::launch_path_s<3, 12>(a, st);
-        case 13: return fixedk::launch_path_s<3, 13>(a, st);
-        case 14: return fixedk::launch_path_s<3, 14>(a, st);
-        case 15: return fixedk::launch_path_s<3, 15>(a, st);
-        case 16: return fixedk::launch_path_s<3, 16>(a, st);
     }
-    return hipErrorInvalidValue;
+    return launch_fixedpath_o3b(a, st);
 }
 
 }  // namespace csp
