@@ -2,6 +2,9 @@
 // Host-side validation, workspace carving, host<->device staging for CSP_MEM_HOST callers and
 // kernel dispatch.  No CPU compute path exists: every entry point ends in a HIP launch or an
 // error code.
+// Layout: helpers (anonymous namespace) first, the extern "C" entries after.  Which kernel a descriptor gets is
+// decided in ONE place, pick_kernel(); the host-memory half of the entries that take waypoints / times / bc and
+// a set of optional outputs goes through ONE staging helper, Stage (with offsets_ok() and sizes_of()).
 #include "../../include/csp_minsnap.h"
 #include "minsnap_launch.h"
 #include "minsnap_hoststage.h"
@@ -43,11 +46,19 @@ struct Shape {
     size_t elt;
 };
 
-int validate(const csp_minsnap_desc *d, Shape &s) {
+// what every entry asks of a descriptor before it reads anything else of it (csp_minsnap_solve_mixed has per-trajectory
+// orders and shapes of its own and stops here)
+int validate_header(const csp_minsnap_desc *d) {
     if (!d) return CSP_ERR_INVALID_ARG;
     if (d->abi_version != CSP_MINSNAP_ABI_VERSION) return CSP_ERR_INVALID_ARG;
     if (d->dtype != CSP_DTYPE_F64 && d->dtype != CSP_DTYPE_F32) return CSP_ERR_INVALID_ARG;
     if (d->mem_space != CSP_MEM_HOST && d->mem_space != CSP_MEM_DEVICE) return CSP_ERR_INVALID_ARG;
+    return CSP_OK;
+}
+
+int validate(const csp_minsnap_desc *d, Shape &s) {
+    int rc = validate_header(d);
+    if (rc != CSP_OK) return rc;
     if (d->order < 1) return CSP_ERR_INVALID_ARG;
     if (d->order > 5) return CSP_ERR_UNSUPPORTED;
     if (d->batch < 0 || d->num_segments < 0) return CSP_ERR_INVALID_ARG;
@@ -68,11 +79,6 @@ int validate(const csp_minsnap_desc *d, Shape &s) {
     return CSP_OK;
 }
 
-bool use_fixed(const csp_minsnap_desc *d, const Shape &s) {
-    if (d->flags & CSP_FLAG_FORCE_GENERIC) return false;
-    return csp::fixed_supported(s.order, s.S, s.f32, d->path_weight, s.ragged, (d->flags & CSP_FLAG_SEGMENT_MAJOR) != 0);
-}
-
 // very long trajectories (256 < S <= 1024; from 17 segments at order 5 or with CSP_FLAG_SPAN): spans of 16 segments per
 // lane (minsnap_span.hip).  Below 257 segments the chunked kernel is faster: the span kernel re-reads its
 // inputs once per elimination step and 2048 resident waves x 34 KB do not stay in L2.
@@ -80,30 +86,35 @@ bool use_fixed(const csp_minsnap_desc *d, const Shape &s) {
 // the batch size) and pins that choice for its per-device chunks, so that sharding never changes the arithmetic.
 thread_local int g_span_override = -1;   // -1: decide here; 0 / 1: decided by the caller
 
-bool use_span(const csp_minsnap_desc *d, const Shape &s) {
-    if ((d->flags & CSP_FLAG_FORCE_GENERIC) || use_fixed(d, s)) return false;
-    if (g_span_override >= 0)
-        return g_span_override == 1 && csp::span_supported(s.order, s.Smax, s.f32 && (d->flags & CSP_FLAG_F32_ARITH), d->path_weight,
-                                                           (d->flags & CSP_FLAG_SEGMENT_MAJOR) != 0);
-    // order 5 (4x4 blocks) is the exception: the chunked kernel needs 392 registers there (one wave per
-    // SIMD) and loses to the span kernel from 17 segments on (measured 1.3-1.75x at S = 20..128)
-    // (with at least a wave per SIMD of span lanes: below that the chunked kernel's 4x more lanes win)
-    const bool o5_big = s.order == 5 && s.Smax > 16 && (s.B << csp::span_lanes_log2(s.Smax)) >= 65536;
-    if (s.Smax <= 256 && !(d->flags & CSP_FLAG_SPAN) && !o5_big) return false;
-    return csp::span_supported(s.order, s.Smax, s.f32 && (d->flags & CSP_FLAG_F32_ARITH), d->path_weight,
-                               (d->flags & CSP_FLAG_SEGMENT_MAJOR) != 0);
+enum class Kernel { Fixed, Span, Chunked, Generic };
+
+// The kernel of a solve, by priority: forced generic, the fixed-size buckets, the span kernel, the chunked kernel, else
+// the generic kernel.
+Kernel pick_kernel(const csp_minsnap_desc *d, const Shape &s) {
+    if (d->flags & CSP_FLAG_FORCE_GENERIC) return Kernel::Generic;
+    const bool seg_major = (d->flags & CSP_FLAG_SEGMENT_MAJOR) != 0, f32_arith = s.f32 && (d->flags & CSP_FLAG_F32_ARITH);
+    if (csp::fixed_supported(s.order, s.S, s.f32, d->path_weight, s.ragged, seg_major)) return Kernel::Fixed;
+    bool span = g_span_override == 1;
+    if (g_span_override < 0) {
+        // order 5 (4x4 blocks) is the exception: the chunked kernel needs 392 registers there (one wave per
+        // SIMD) and loses to the span kernel from 17 segments on (measured 1.3-1.75x at S = 20..128)
+        // (with at least a wave per SIMD of span lanes: below that the chunked kernel's 4x more lanes win)
+        const bool o5_big = s.order == 5 && s.Smax > 16 && (s.B << csp::span_lanes_log2(s.Smax)) >= 65536;
+        span = s.Smax > 256 || (d->flags & CSP_FLAG_SPAN) || o5_big;
+    }
+    if (span && csp::span_supported(s.order, s.Smax, f32_arith, d->path_weight, seg_major)) return Kernel::Span;
+    // the multi-lane workspace-free kernel takes what the fixed buckets and the span kernel do not: short
+    // ragged batches, fp32 storage at S <= 16 (minsnap_chunked.hip)
+    if (csp::chunked_supported(s.order, s.Smax, f32_arith, d->path_weight, seg_major)) return Kernel::Chunked;
+    return Kernel::Generic;
 }
 
-// the multi-lane workspace-free kernel takes what the fixed buckets and the span kernel do not: short
-// ragged batches, fp32 storage at S <= 16 (minsnap_chunked.hip)
-bool use_chunked(const csp_minsnap_desc *d, const Shape &s) {
-    if ((d->flags & CSP_FLAG_FORCE_GENERIC) || use_fixed(d, s) || use_span(d, s)) return false;
-    return csp::chunked_supported(s.order, s.Smax, s.f32 && (d->flags & CSP_FLAG_F32_ARITH), d->path_weight,
-                                  (d->flags & CSP_FLAG_SEGMENT_MAJOR) != 0);
-}
+bool use_fixed(const csp_minsnap_desc *d, const Shape &s) { return pick_kernel(d, s) == Kernel::Fixed; }
 
-size_t ws_bytes(const csp_minsnap_desc *d, const Shape &s, size_t *tstar_off) {
-    if (use_fixed(d, s) || use_span(d, s) || use_chunked(d, s)) { if (tstar_off) *tstar_off = 0; return 0; }
+// only the generic kernel needs a workspace: its factors, then (path penalty) the t* indices at *tstar_off
+size_t ws_bytes(const csp_minsnap_desc *d, const Shape &s, Kernel k, size_t *tstar_off = nullptr) {
+    if (tstar_off) *tstar_off = 0;
+    if (k != Kernel::Generic) return 0;
     const size_t ws_elt = (s.f32 && (d->flags & CSP_FLAG_F32_ARITH)) ? 4 : 8;  // workspace holds the arithmetic type
     size_t factors = align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::generic_ws_entries(s.order) *
                                   (size_t)s.B * ws_elt, 256);
@@ -111,6 +122,7 @@ size_t ws_bytes(const csp_minsnap_desc *d, const Shape &s, size_t *tstar_off) {
     size_t ts = d->path_weight > 0.0 ? align_up((size_t)s.Smax * (size_t)s.B * sizeof(int), 256) : 0;
     return factors + ts;
 }
+size_t ws_bytes(const csp_minsnap_desc *d, const Shape &s) { return ws_bytes(d, s, pick_kernel(d, s)); }
 
 int select_device(int device_id) {
     int n = 0;
@@ -138,6 +150,62 @@ int current_device() {
     return cur;
 }
 
+// ---- CSP_MEM_HOST callers: sizes from the caller's host arrays, staging through the cached arena (minsnap_hoststage.h) ----
+
+// ragged host-memory batch: every trajectory has 0 .. max_segments segments (the offsets are the caller's host array)
+bool offsets_ok(const csp_minsnap_desc *d, const Shape &s) {
+    for (int64_t b = 0; s.ragged && b < s.B; ++b) {
+        const int64_t n = d->seg_offsets[b + 1] - d->seg_offsets[b];
+        if (n < 0 || n > s.Smax) return false;
+    }
+    return true;
+}
+
+// Bytes of a call's arrays.  An open trajectory of n segments has n + 1 waypoints, a closed loop n.
+struct Sizes {
+    int64_t total_seg;
+    size_t wp, tm, bc, co;
+};
+Sizes sizes_of(const csp_minsnap_desc *d, const Shape &s, bool closed_loop = false) {
+    Sizes z;
+    z.total_seg = s.ragged ? d->seg_offsets[s.B] : s.B * (int64_t)s.S;
+    z.wp = (size_t)(z.total_seg + (closed_loop ? 0 : s.B)) * 3 * s.elt;
+    z.tm = (size_t)z.total_seg * s.elt;
+    z.bc = (size_t)(d->bc_per_trajectory ? s.B : 1) * 12 * s.elt;
+    z.co = (size_t)z.total_seg * 3 * 2 * (size_t)s.order * s.elt;
+    return z;
+}
+
+// One synchronous host-memory call of an entry that takes waypoints / times / bc (bc_host null: a closed loop) and
+// writes outputs the caller may leave out: the common inputs are registered here, the entry adds what is its own
+// (HostCall's rule holds: every in() before every out() before scratch()) and hands its dispatch_* to run().
+// A buffer the caller passed as null is not registered and its ptr() is null: the device-memory form's "absent".
+struct Stage {
+    static constexpr size_t ABSENT = (size_t)-1;
+    csp::HostCall hc;
+    const Sizes z;
+    size_t wp, tm, bc, seg_off, vw_per;
+    Stage(const csp_minsnap_desc *d, const Shape &s, hipStream_t st, const void *waypoints, const void *times, const void *bc_host)
+        : hc(current_device(), st), z(sizes_of(d, s, bc_host == nullptr)) {
+        wp = in(waypoints, z.wp);
+        tm = in(times, z.tm);
+        bc = in(bc_host, z.bc);
+        seg_off = in(s.ragged ? d->seg_offsets : nullptr, (size_t)(s.B + 1) * 8);
+        vw_per = in(d->vel_zero_weight_per_traj, (size_t)s.B * 8);
+    }
+    size_t in(const void *host, size_t bytes) { return host ? hc.in(host, bytes) : ABSENT; }
+    size_t out(void *host, size_t bytes) { return host ? hc.out(host, bytes) : ABSENT; }
+    template <class T = void> T *ptr(size_t off) const { return off == ABSENT ? nullptr : hc.ptr<T>(off); }
+    // upload, the entry's launches, download; a failed launch leaves the arena to ~HostCall
+    template <class Launch> int run(Launch &&launch) {
+        CSP_HIP(hc.upload());
+        const int rc = launch();
+        if (rc != CSP_OK) return rc;
+        CSP_HIP(hc.download());
+        return CSP_OK;
+    }
+};
+
 // Smallest double x with sqrt(x) >= d under IEEE rounding (sqrt is monotone), so that the kernels can
 // test the squared distance: d2 >= x  <=>  sqrt(d2) >= d.  d <= 0 keeps everything (x = 0), NaN nothing.
 double keep_threshold(double d) {
@@ -154,8 +222,9 @@ double keep_threshold(double d) {
 int dispatch(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const void *bc,
              void *co, double *max_dev, int32_t *status, const int64_t *seg_off, const double *vw_per,
              void *ws, size_t ws_size, hipStream_t st, const int32_t *skip = nullptr, int *tau_buf = nullptr, int tau_mode = 0) {
+    const Kernel k = pick_kernel(d, s);
     size_t tstar_off = 0;
-    const size_t need = ws_bytes(d, s, &tstar_off);
+    const size_t need = ws_bytes(d, s, k, &tstar_off);
     if (need > 0 && (!ws || ws_size < need)) return CSP_ERR_WORKSPACE;
     csp::GenericArgs a;
     a.wp = wp; a.times = tm; a.bc = bc; a.coeffs = co; a.max_dev = max_dev; a.status = status;
@@ -173,17 +242,25 @@ int dispatch(const csp_minsnap_desc *d, const Shape &s, const void *wp, const vo
     a.skip = skip;
     a.tau_mode = 0;
     // inside the re-solve loop: the path kernel keeps its t* indices in tau_buf, the generic kernel in its workspace
-    if (use_fixed(d, s)) { if (tau_buf) { a.tstar = tau_buf; a.tau_mode = tau_mode; } }
-    else a.tau_mode = tau_mode;
-    // the fixed kernel moves 16-byte pieces (LDS-DMA, ds_read_b128, dwordx4 stores)
-    const bool aligned = (((uintptr_t)wp | (uintptr_t)tm | (uintptr_t)co) & 15u) == 0;
-    if (use_fixed(d, s) && !aligned) return CSP_ERR_INVALID_ARG;
-    // the chunked kernel reads scalars and stores 16-byte pieces (8-byte for fp32 with odd order)
-    if ((use_chunked(d, s) || use_span(d, s)) && ((uintptr_t)co & ((s.f32 && (s.order & 1)) ? 7u : 15u))) return CSP_ERR_INVALID_ARG;
-    hipError_t e = use_fixed(d, s) ? csp::launch_fixed(a, st)
-                 : use_span(d, s)    ? csp::launch_span(a, s.f32, s.Smax, st)
-                 : use_chunked(d, s) ? csp::launch_chunked(a, s.f32, s.Smax, st)
-                                     : csp::launch_generic(a, s.f32, (d->flags & CSP_FLAG_F32_ARITH) != 0, st);
+    if (k != Kernel::Fixed) a.tau_mode = tau_mode;
+    else if (tau_buf) { a.tstar = tau_buf; a.tau_mode = tau_mode; }
+    hipError_t e = hipSuccess;
+    switch (k) {
+        case Kernel::Fixed:
+            // the fixed kernel moves 16-byte pieces (LDS-DMA, ds_read_b128, dwordx4 stores)
+            if ((((uintptr_t)wp | (uintptr_t)tm | (uintptr_t)co) & 15u) != 0) return CSP_ERR_INVALID_ARG;
+            e = csp::launch_fixed(a, st);
+            break;
+        case Kernel::Span:
+        case Kernel::Chunked:
+            // the chunked kernel reads scalars and stores 16-byte pieces (8-byte for fp32 with odd order)
+            if ((uintptr_t)co & ((s.f32 && (s.order & 1)) ? 7u : 15u)) return CSP_ERR_INVALID_ARG;
+            e = k == Kernel::Span ? csp::launch_span(a, s.f32, s.Smax, st) : csp::launch_chunked(a, s.f32, s.Smax, st);
+            break;
+        case Kernel::Generic:
+            e = csp::launch_generic(a, s.f32, (d->flags & CSP_FLAG_F32_ARITH) != 0, st);
+            break;
+    }
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return CSP_OK;
 }
@@ -282,7 +359,7 @@ struct RcclTransport {
             }
             Shape ps;
             if (validate(&pd, ps) != CSP_OK) return CSP_ERR_INVALID_ARG;
-            d.ws_bytes = ws_bytes(&pd, ps, nullptr);
+            d.ws_bytes = ws_bytes(&pd, ps);
             if (g == root && d.ws_bytes == 0) continue;
             d.arena = csp::arena_acquire(node->devs[(size_t)g]);
             size_t top = 0;
@@ -450,13 +527,148 @@ int solve_sharded_device(const csp_minsnap_desc *desc, const Shape &s, const voi
     t.wp = (const char *)waypoints; t.tm = (const char *)times; t.bc = (const char *)bc;
     t.co = (char *)coeffs; t.max_dev = max_dev; t.status = status;
     const int span_before = g_span_override;
-    g_span_override = use_span(desc, s) ? 1 : 0;   // decided from the WHOLE batch, pinned for the pieces
+    g_span_override = pick_kernel(desc, s) == Kernel::Span ? 1 : 0;   // decided from the WHOLE batch, pinned for the pieces
     rc = t.setup();
     if (rc == CSP_OK) rc = csp::shard::run(t, s.B, ngpu, 0, t.nchunks);
     if (rc != CSP_OK) (void)t.finish();
     t.teardown();
     g_span_override = span_before;
     return rc;
+}
+
+// ---- the differentiable solve, the snap cost / time optimiser and the periodic solve: limits, workspaces, dispatch ----
+
+// csp_minsnap_solve_batch_vjp's own limits on top of validate(): no path penalty (t* is a discrete arg-max and the
+// penalty's chord point depends on T), orders 2..5, trajectory-major coefficients, fp64 arithmetic.
+int validate_vjp(const csp_minsnap_desc *d, Shape &s) {
+    int rc = validate(d, s);
+    if (rc != CSP_OK) return rc;
+    if (d->order < 2) return CSP_ERR_UNSUPPORTED;
+    if (d->path_weight != 0.0) return CSP_ERR_UNSUPPORTED;
+    if (d->flags & (CSP_FLAG_SEGMENT_MAJOR | CSP_FLAG_F32_ARITH)) return CSP_ERR_UNSUPPORTED;
+    return CSP_OK;
+}
+
+size_t vjp_ws_bytes(const csp_minsnap_desc *d, const Shape &s, size_t *part_off) {
+    const size_t factors = align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::vjp_ws_entries(s.order) * (size_t)s.B * 8, 256);
+    if (part_off) *part_off = factors;
+    return factors + (d->bc_per_trajectory ? 0 : 12 * (size_t)csp::vjp_blocks(s.B) * 8);
+}
+
+int dispatch_vjp(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const void *bc, const void *gco,
+                 void *gwp, void *gtm, void *gbc, int32_t *status, const int64_t *seg_off, const double *vw_per, void *ws,
+                 size_t ws_size, hipStream_t st) {
+    size_t part_off = 0;
+    const size_t need = vjp_ws_bytes(d, s, &part_off);
+    if (need > 0 && (!ws || ws_size < need)) return CSP_ERR_WORKSPACE;
+    if ((uintptr_t)ws & 7u) return CSP_ERR_WORKSPACE;
+    if ((uintptr_t)gco & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // p_bar records are read as 2-element vectors
+    csp::VjpArgs a;
+    a.wp = wp; a.times = tm; a.bc = bc; a.grad_coeffs = gco;
+    a.grad_wp = gwp; a.grad_times = gtm; a.grad_bc = gbc; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.ws = ws;
+    a.bc_part = (gbc && !d->bc_per_trajectory) ? (void *)((char *)ws + part_off) : nullptr;
+    a.vw_per = vw_per;
+    a.vel_zero_weight = d->vel_zero_weight;
+    a.B = s.B; a.S = s.S; a.order = s.order; a.bc_per_traj = d->bc_per_trajectory ? 1 : 0;
+    hipError_t e = csp::launch_vjp(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, "vjp kernel launch");
+    return CSP_OK;
+}
+
+// csp_minsnap_cost_batch / csp_minsnap_optimize_times_batch: the VJP's scope (validate_vjp).
+size_t cost_ws_bytes(const Shape &s) {
+    return align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::timeopt_ws_entries(s.order) * (size_t)s.B * 8, 256);
+}
+
+size_t timeopt_ws_bytes(const Shape &s, size_t *vec_off) {
+    const size_t factors = cost_ws_bytes(s);
+    if (vec_off) *vec_off = factors;
+    return factors + 4 * (size_t)s.Smax * (size_t)s.B * 8;
+}
+
+int validate_timeopt(const csp_minsnap_desc *d, const csp_minsnap_timeopt_params *p, Shape &s) {
+    int rc = validate_vjp(d, s);
+    if (rc != CSP_OK) return rc;
+    if (!p || p->abi_version != CSP_MINSNAP_ABI_VERSION) return CSP_ERR_INVALID_ARG;
+    if (p->mode != CSP_TIMEOPT_FIXED_TOTAL && p->mode != CSP_TIMEOPT_TIME_PENALTY) return CSP_ERR_INVALID_ARG;
+    if (p->mode == CSP_TIMEOPT_TIME_PENALTY && !(p->time_weight > 0.0 && std::isfinite(p->time_weight))) return CSP_ERR_INVALID_ARG;
+    if (!(p->min_time > 0.0 && std::isfinite(p->min_time))) return CSP_ERR_INVALID_ARG;
+    if (!(p->tol >= 0.0) || p->max_iters < 0) return CSP_ERR_INVALID_ARG;
+    return CSP_OK;
+}
+
+// FIXED_TOTAL needs sum_j T_j >= S * min_time for every trajectory: checked on the host when the times are host memory.
+bool totals_feasible(const Shape &s, const int64_t *seg_off, const void *times, double tmin) {
+    for (int64_t b = 0; b < s.B; ++b) {
+        const int64_t s0 = s.ragged ? seg_off[b] : b * (int64_t)s.S, s1 = s.ragged ? seg_off[b + 1] : s0 + s.S;
+        double c = 0.0;
+        for (int64_t j = s0; j < s1; ++j) c += s.f32 ? (double)((const float *)times)[j] : ((const double *)times)[j];
+        if (c < (double)(s1 - s0) * tmin) return false;
+    }
+    return true;
+}
+
+void timeopt_args(const csp_minsnap_desc *d, const Shape &s, csp::TimeOptArgs &a) {
+    a = csp::TimeOptArgs{};
+    a.vel_zero_weight = d->vel_zero_weight;
+    a.B = s.B; a.S = s.S; a.Smax = s.Smax; a.order = s.order; a.bc_per_traj = d->bc_per_trajectory ? 1 : 0;
+}
+
+int dispatch_cost(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const void *bc, double *cost,
+                  void *grad, int32_t *status, const int64_t *seg_off, const double *vw_per, void *ws, size_t ws_size,
+                  hipStream_t st) {
+    const size_t need = cost_ws_bytes(s);
+    if (need > 0 && (!ws || ws_size < need)) return CSP_ERR_WORKSPACE;
+    if ((uintptr_t)ws & 7u) return CSP_ERR_WORKSPACE;
+    csp::TimeOptArgs a;
+    timeopt_args(d, s, a);
+    a.wp = wp; a.times = tm; a.bc = bc; a.cost = cost; a.grad = grad; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.ws = ws; a.vw_per = vw_per;
+    hipError_t e = csp::launch_cost(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, "cost kernel launch");
+    return CSP_OK;
+}
+
+int dispatch_timeopt(const csp_minsnap_desc *d, const csp_minsnap_timeopt_params *p, const Shape &s, const void *wp,
+                     const void *tm, const void *bc, void *tout, void *co, double *obj, int32_t *iters, int32_t *status,
+                     const int64_t *seg_off, const double *vw_per, void *ws, size_t ws_size, hipStream_t st) {
+    size_t vec_off = 0;
+    const size_t need = timeopt_ws_bytes(s, &vec_off);
+    if (!ws || ws_size < need || ((uintptr_t)ws & 7u)) return CSP_ERR_WORKSPACE;
+    csp::TimeOptArgs a;
+    timeopt_args(d, s, a);
+    a.wp = wp; a.times = tm; a.bc = bc; a.times_out = tout; a.objective = obj; a.iterations = iters; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.ws = ws; a.vec = (double *)((char *)ws + vec_off); a.vw_per = vw_per;
+    a.mode = p->mode == CSP_TIMEOPT_FIXED_TOTAL ? csp::CSP_TIMEOPT_FIXED_TOTAL_V : csp::CSP_TIMEOPT_TIME_PENALTY_V;
+    a.time_weight = p->time_weight; a.min_time = p->min_time; a.tol = p->tol; a.max_iters = p->max_iters;
+    hipError_t e = csp::launch_timeopt(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, "time optimiser launch");
+    if (!co) return CSP_OK;
+    // the coefficients are csp_minsnap_solve_batch's at the optimised times; its workspace (0 or the generic kernel's
+    // factors, the same size as ours) is the factor region
+    return dispatch(d, s, wp, tout, bc, co, nullptr, nullptr, seg_off, vw_per, ws, vec_off, st);
+}
+
+// csp_minsnap_solve_periodic_batch: the VJP's scope (validate_vjp); bc_per_trajectory is ignored (there is no bc).
+size_t periodic_ws_bytes(const Shape &s) {
+    return align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::periodic_ws_entries(s.order) * (size_t)s.B * 8, 256);
+}
+
+int dispatch_periodic(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, void *co, double *cost,
+                      void *grad, int32_t *status, const int64_t *seg_off, const double *vw_per, void *ws, hipStream_t st) {
+    csp::PeriodicArgs a{};
+    a.wp = wp; a.times = tm; a.coeffs = co; a.cost = cost; a.grad = grad; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.ws = ws; a.vw_per = vw_per;
+    a.vel_zero_weight = d->vel_zero_weight;
+    a.B = s.B; a.S = s.S; a.order = s.order;
+    hipError_t e = csp::launch_periodic(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, "periodic kernel launch");
+    return CSP_OK;
 }
 
 }  // namespace
@@ -492,26 +704,26 @@ int csp_minsnap_device_count(void) {
 size_t csp_minsnap_workspace_bytes(const csp_minsnap_desc *desc) {
     Shape s;
     if (validate(desc, s) != CSP_OK) return 0;
-    return ws_bytes(desc, s, nullptr);
+    return ws_bytes(desc, s);
 }
 
 const char *csp_minsnap_kernel_name(const csp_minsnap_desc *desc) {
     static thread_local char name[64];
     Shape s;
     if (validate(desc, s) != CSP_OK) return nullptr;
-    if (use_fixed(desc, s)) return csp::fixed_kernel_name(s.order, s.S, desc->path_weight > 0.0);
-    if (use_span(desc, s)) {
-        std::snprintf(name, sizeof name, "span_o%d_%s_l%d%s", s.order, s.f32 ? "f32io_f64" : "f64",
-                      1 << csp::span_lanes_log2(s.Smax), s.ragged ? "_ragged" : "");
-        return name;
+    const char *io = s.f32 ? "f32io_f64" : "f64", *rag = s.ragged ? "_ragged" : "";
+    switch (pick_kernel(desc, s)) {
+        case Kernel::Fixed: return csp::fixed_kernel_name(s.order, s.S, desc->path_weight > 0.0);
+        case Kernel::Span:
+            std::snprintf(name, sizeof name, "span_o%d_%s_l%d%s", s.order, io, 1 << csp::span_lanes_log2(s.Smax), rag);
+            break;
+        case Kernel::Chunked:
+            std::snprintf(name, sizeof name, "chunked_o%d_%s_l%d%s", s.order, io, 1 << csp::chunked_lanes_log2(s.Smax), rag);
+            break;
+        case Kernel::Generic:
+            std::snprintf(name, sizeof name, "generic_o%d_%s%s", s.order, (s.f32 && (desc->flags & CSP_FLAG_F32_ARITH)) ? "f32" : io, rag);
+            break;
     }
-    if (use_chunked(desc, s)) {
-        std::snprintf(name, sizeof name, "chunked_o%d_%s_l%d%s", s.order, s.f32 ? "f32io_f64" : "f64",
-                      1 << csp::chunked_lanes_log2(s.Smax), s.ragged ? "_ragged" : "");
-        return name;
-    }
-    std::snprintf(name, sizeof name, "generic_o%d_%s%s", s.order,
-                  !s.f32 ? "f64" : ((desc->flags & CSP_FLAG_F32_ARITH) ? "f32" : "f32io_f64"), s.ragged ? "_ragged" : "");
     return name;
 }
 
@@ -532,35 +744,15 @@ int csp_minsnap_solve_batch(const csp_minsnap_desc *desc, const void *waypoints,
                         desc->vel_zero_weight_per_traj, workspace, workspace_bytes, st);
 
     // CSP_MEM_HOST: stage through a cached per-device arena (minsnap_hoststage.h), synchronously.
-    int64_t total_seg;
-    if (s.ragged) {
-        total_seg = desc->seg_offsets[s.B];
-        for (int64_t b = 0; b < s.B; ++b) {
-            const int64_t n = desc->seg_offsets[b + 1] - desc->seg_offsets[b];
-            if (n < 0 || n > s.Smax) return CSP_ERR_INVALID_ARG;
-        }
-    } else {
-        total_seg = s.B * (int64_t)s.S;
-    }
-    const size_t m = 2 * (size_t)s.order;
-    const size_t n_wp = (size_t)(total_seg + s.B) * 3 * s.elt, n_tm = (size_t)total_seg * s.elt;
-    const size_t n_bc = (size_t)(desc->bc_per_trajectory ? s.B : 1) * 12 * s.elt;
-    const size_t n_co = (size_t)total_seg * 3 * m * s.elt;
-    const size_t n_ws = ws_bytes(desc, s, nullptr);
-    csp::HostCall hc(current_device(), st);
-    const size_t o_wp = hc.in(waypoints, n_wp), o_tm = hc.in(times, n_tm), o_bc = hc.in(bc, n_bc);
-    const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
-    const size_t o_vw = desc->vel_zero_weight_per_traj ? hc.in(desc->vel_zero_weight_per_traj, (size_t)s.B * 8) : 0;
-    const size_t o_co = hc.out(coeffs, n_co);
-    const size_t o_md = max_dev ? hc.out(max_dev, (size_t)s.B * 8) : 0, o_st = status ? hc.out(status, (size_t)s.B * 4) : 0;
-    const size_t o_ws = hc.scratch(n_ws);
-    CSP_HIP(hc.upload());
-    rc = dispatch(desc, s, hc.ptr(o_wp), hc.ptr(o_tm), hc.ptr(o_bc), hc.ptr(o_co), max_dev ? hc.ptr<double>(o_md) : nullptr,
-                  status ? hc.ptr<int32_t>(o_st) : nullptr, s.ragged ? hc.ptr<const int64_t>(o_so) : nullptr,
-                  desc->vel_zero_weight_per_traj ? hc.ptr<const double>(o_vw) : nullptr, hc.ptr(o_ws), n_ws, st);
-    if (rc != CSP_OK) return rc;
-    CSP_HIP(hc.download());
-    return CSP_OK;
+    if (!offsets_ok(desc, s)) return CSP_ERR_INVALID_ARG;
+    const size_t n_ws = ws_bytes(desc, s);
+    Stage g(desc, s, st, waypoints, times, bc);
+    const size_t o_co = g.out(coeffs, g.z.co), o_md = g.out(max_dev, (size_t)s.B * 8), o_st = g.out(status, (size_t)s.B * 4);
+    const size_t o_ws = g.hc.scratch(n_ws);
+    return g.run([&] {
+        return dispatch(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(g.bc), g.ptr(o_co), g.ptr<double>(o_md), g.ptr<int32_t>(o_st),
+                        g.ptr<const int64_t>(g.seg_off), g.ptr<const double>(g.vw_per), g.ptr(o_ws), n_ws, st);
+    });
 }
 
 int csp_minsnap_solve_multi(const csp_minsnap_desc *desc, int n, const int64_t *batches, const void *const *waypoints,
@@ -595,7 +787,7 @@ int csp_minsnap_solve_multi(const csp_minsnap_desc *desc, int n, const int64_t *
             dk.batch = batches[k];
             Shape sk;
             if ((rc = validate(&dk, sk)) != CSP_OK) return rc;
-            if (ws_bytes(&dk, sk, nullptr) != 0) return CSP_ERR_UNSUPPORTED;
+            if (ws_bytes(&dk, sk) != 0) return CSP_ERR_UNSUPPORTED;
             rc = dispatch(&dk, sk, waypoints[k], times[k], bc[k], coeffs[k], nullptr, status ? status[k] : nullptr, nullptr, nullptr, nullptr, 0, st);
             if (rc != CSP_OK) return rc;
         }
@@ -637,16 +829,15 @@ size_t csp_minsnap_mixed_workspace_bytes(const csp_minsnap_desc *desc) {
 int csp_minsnap_solve_mixed(const csp_minsnap_desc *desc, const int32_t *orders, const void *waypoints, const void *times,
                             const void *bc, void *coeffs, int64_t *coeff_offsets_out, int32_t *status,
                             void *workspace, size_t workspace_bytes, void *hip_stream) {
-    if (!desc || desc->abi_version != CSP_MINSNAP_ABI_VERSION) return CSP_ERR_INVALID_ARG;
-    if (desc->dtype != CSP_DTYPE_F64 && desc->dtype != CSP_DTYPE_F32) return CSP_ERR_INVALID_ARG;
-    if (desc->mem_space != CSP_MEM_HOST && desc->mem_space != CSP_MEM_DEVICE) return CSP_ERR_INVALID_ARG;
+    int rc = validate_header(desc);
+    if (rc != CSP_OK) return rc;
     if (desc->batch < 0 || desc->vel_zero_weight < 0.0 || desc->path_weight < 0.0) return CSP_ERR_INVALID_ARG;
     if (desc->path_weight != 0.0 || (desc->flags & (CSP_FLAG_F32_ARITH | CSP_FLAG_SEGMENT_MAJOR))) return CSP_ERR_UNSUPPORTED;
     if (desc->batch == 0) return CSP_OK;
     if (desc->batch > 0x7fffffff) return CSP_ERR_INVALID_ARG;   // trajectory indices are int32 on the device
     if (!desc->seg_offsets || desc->max_segments < 1 || desc->max_segments > 256) return CSP_ERR_INVALID_ARG;
     if (!orders || !waypoints || !times || !bc || !coeffs) return CSP_ERR_INVALID_ARG;
-    int rc = select_device(desc->device_id);
+    rc = select_device(desc->device_id);
     if (rc != CSP_OK) return rc;
     hipStream_t st = (hipStream_t)hip_stream;
     const bool f32 = desc->dtype == CSP_DTYPE_F32;
@@ -728,7 +919,7 @@ int csp_minsnap_solve_batch_sharded(const csp_minsnap_desc *desc, const void *wa
     if ((int64_t)ngpu > s.B) ngpu = (int)s.B;
     if (desc->mem_space == CSP_MEM_DEVICE)   // the batch lives on a root device: scatter / solve / gather over RCCL
         return solve_sharded_device(desc, s, waypoints, times, bc, coeffs, max_dev, status, ordinals, ngpu);
-    const int span_choice = use_span(desc, s) ? 1 : 0;   // from the WHOLE batch; pinned for every chunk
+    const int span_choice = pick_kernel(desc, s) == Kernel::Span ? 1 : 0;   // from the WHOLE batch; pinned for every chunk
     const size_t m = 2 * (size_t)s.order;
     struct Chunk {
         csp_minsnap_desc d;
@@ -795,12 +986,11 @@ int csp_minsnap_time_alloc_batch(const csp_minsnap_desc *desc, const void *waypo
         hipError_t e = csp::launch_time_alloc(a, s.f32, st);
         return e == hipSuccess ? CSP_OK : hip_fail(e, "time_alloc launch");
     }
-    const int64_t total_seg = s.ragged ? desc->seg_offsets[s.B] : s.B * (int64_t)s.S;
-    const size_t n_wp = (size_t)(total_seg + s.B) * 3 * s.elt, n_tm = (size_t)total_seg * s.elt;
+    const Sizes z = sizes_of(desc, s);
     csp::HostCall hc(current_device(), st);
-    const size_t o_wp = hc.in(waypoints, n_wp);
+    const size_t o_wp = hc.in(waypoints, z.wp);
     const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
-    const size_t o_tm = hc.out(times, n_tm);
+    const size_t o_tm = hc.out(times, z.tm);
     CSP_HIP(hc.upload());
     a.wp = hc.ptr(o_wp); a.times = hc.ptr(o_tm); a.seg_off = s.ragged ? hc.ptr<const int64_t>(o_so) : nullptr;
     hipError_t e = csp::launch_time_alloc(a, s.f32, st);
@@ -817,8 +1007,9 @@ size_t csp_minsnap_plan_workspace_bytes(const csp_minsnap_desc *desc) {
     validate(&g, gs);
     // solve workspace + vw[B] f64 + max_dev[B] f64 + iters[B] i32 + done[B] i32 + the count of unfinished trajectories (i32)
     // + t* indices [S][B] i32 (path kernel)
-    const size_t tau = (desc->path_weight > 0.0 && use_fixed(&g, gs)) ? align_up((size_t)s.B * (size_t)s.S * 4, 256) : 0;
-    return align_up(ws_bytes(&g, gs, nullptr), 256) + align_up((size_t)s.B * 8, 256) * 2 + align_up((size_t)s.B * 4, 256) * 2 + 256 + tau;
+    const Kernel k = pick_kernel(&g, gs);
+    const size_t tau = (desc->path_weight > 0.0 && k == Kernel::Fixed) ? align_up((size_t)s.B * (size_t)s.S * 4, 256) : 0;
+    return align_up(ws_bytes(&g, gs, k), 256) + align_up((size_t)s.B * 8, 256) * 2 + align_up((size_t)s.B * 4, 256) * 2 + 256 + tau;
 }
 
 }  // extern "C"
@@ -867,7 +1058,8 @@ int plan_device(const csp_minsnap_desc *desc, const Shape &s, const void *waypoi
     validate(&g, gs);
     const size_t need = csp_minsnap_plan_workspace_bytes(desc);
     if (!workspace || workspace_bytes < need) return CSP_ERR_WORKSPACE;
-    const size_t solve_ws = align_up(ws_bytes(&g, gs, nullptr), 256);
+    const Kernel k = pick_kernel(&g, gs);
+    const size_t solve_ws = align_up(ws_bytes(&g, gs, k), 256);
     char *base = (char *)workspace + solve_ws;
     // the loop's per-trajectory state lives in the caller's output arrays where they were passed (no copy at the end)
     double *vw = vel_zero_weight_out ? vel_zero_weight_out : (double *)base;   base += align_up((size_t)s.B * 8, 256);
@@ -876,7 +1068,7 @@ int plan_device(const csp_minsnap_desc *desc, const Shape &s, const void *waypoi
     int32_t *done = (int32_t *)base;                              base += align_up((size_t)s.B * 4, 256);
     int32_t *pending = pending_ext ? pending_ext : (int32_t *)base;   base += 256;   // cumulative count of weight increases
     // the pre-solve does not depend on vel_zero_weight: the first pass stores its t* indices, the others reuse them
-    int *tau_buf = use_fixed(&g, gs) ? (int *)base : nullptr;
+    int *tau_buf = k == Kernel::Fixed ? (int *)base : nullptr;
     if (phase != 2) {
         // per-trajectory starting weights: the init kernel leaves vw alone (vel_zero_weight_out may BE the caller's weight
         // array -- an in-place update -- and must not be overwritten with the scalar first), then they are copied in
@@ -934,18 +1126,15 @@ int csp_minsnap_plan_batch(const csp_minsnap_desc *desc, const void *waypoints, 
                            status, workspace, workspace_bytes, st, false);
 
     // CSP_MEM_HOST: stage through the device's cached arena, then run the device-memory form
-    const int64_t total_seg = s.ragged ? desc->seg_offsets[s.B] : s.B * (int64_t)s.S;
-    const size_t m = 2 * (size_t)s.order;
-    const size_t n_wp = (size_t)(total_seg + s.B) * 3 * s.elt, n_tm = (size_t)total_seg * s.elt;
-    const size_t n_bc = (size_t)(desc->bc_per_trajectory ? s.B : 1) * 12 * s.elt, n_co = (size_t)total_seg * 3 * m * s.elt;
+    const Sizes z = sizes_of(desc, s);
     csp_minsnap_desc dd = *desc;
     dd.mem_space = CSP_MEM_DEVICE;
     const size_t n_ws = csp_minsnap_plan_workspace_bytes(&dd);
     csp::HostCall hc(current_device(), st);
-    const size_t o_wp = hc.in(waypoints, n_wp), o_bc = hc.in(bc, n_bc);
+    const size_t o_wp = hc.in(waypoints, z.wp), o_bc = hc.in(bc, z.bc);
     const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
     const size_t o_vi = desc->vel_zero_weight_per_traj ? hc.in(desc->vel_zero_weight_per_traj, (size_t)s.B * 8) : 0;
-    const size_t o_tm = hc.out(times, n_tm), o_co = hc.out(coeffs, n_co);
+    const size_t o_tm = hc.out(times, z.tm), o_co = hc.out(coeffs, z.co);
     const size_t o_md = hc.out(max_dev, (size_t)s.B * 8), o_vw = hc.out(vel_zero_weight_out, (size_t)s.B * 8);
     const size_t o_it = hc.out(iterations, (size_t)s.B * 4), o_st = hc.out(status, (size_t)s.B * 4);
     int32_t raised = 0;
@@ -1014,8 +1203,7 @@ int csp_minsnap_sample_batch(const csp_minsnap_desc *desc, const void *times, co
         }
         a.long_segments = cand > 128.0 * (double)total_seg;
     }
-    const size_t m = 2 * (size_t)s.order;
-    const size_t n_tm = (size_t)total_seg * s.elt, n_co = (size_t)total_seg * 3 * m * s.elt;
+    const Sizes z = sizes_of(desc, s);
     const size_t n_sm = (size_t)s.B * (size_t)capacity * 3 * s.elt;
     // A few long flights (the reference's own call: ONE flight of kilometre legs): one wave per SEGMENT into per-segment
     // runs, then placement + end-point rule + statistics (minsnap_plan.hip sample_wave_seg_kernel).  Needs fp64 storage,
@@ -1042,7 +1230,7 @@ int csp_minsnap_sample_batch(const csp_minsnap_desc *desc, const void *times, co
         if (!fits) run_off.clear();
     }
     csp::HostCall hc(current_device(), st);
-    const size_t o_tm = hc.in(times, n_tm), o_co = hc.in(coeffs, n_co);
+    const size_t o_tm = hc.in(times, z.tm), o_co = hc.in(coeffs, z.co);
     const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
     const size_t o_ro = !run_off.empty() ? hc.in(run_off.data(), run_off.size() * 8) : 0;
     const size_t o_ct = hc.out(counts, (size_t)s.B * 4), o_sx = hc.out(stats, (size_t)s.B * 16);
@@ -1187,9 +1375,7 @@ int csp_minsnap_generate_batch(const csp_minsnap_desc *desc, const void *waypoin
         }
         if (!fits) run_off.clear();
     }
-    const size_t m = 2 * (size_t)s.order;
-    const size_t n_wp = (size_t)(total_seg + s.B) * 3 * s.elt, n_tm = (size_t)total_seg * s.elt;
-    const size_t n_bc = (size_t)(desc->bc_per_trajectory ? s.B : 1) * 12 * s.elt, n_co = (size_t)total_seg * 3 * m * s.elt;
+    const Sizes z = sizes_of(desc, s);
     const size_t n_sm = (size_t)s.B * (size_t)capacity * 3 * s.elt;
     csp_minsnap_desc dd = *desc;
     dd.mem_space = CSP_MEM_DEVICE;
@@ -1197,7 +1383,7 @@ int csp_minsnap_generate_batch(const csp_minsnap_desc *desc, const void *waypoin
     // one flight with a large `capacity` (an upper bound: every candidate): beyond 1 MB only the rows in use come back
     const bool two_step = s.B == 1 && n_sm > ((size_t)1 << 20);
     csp::HostCall hc(current_device(), st);
-    const size_t o_wp = hc.in(waypoints, n_wp), o_bc = hc.in(bc, n_bc);
+    const size_t o_wp = hc.in(waypoints, z.wp), o_bc = hc.in(bc, z.bc);
     const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
     const size_t o_vi = desc->vel_zero_weight_per_traj ? hc.in(desc->vel_zero_weight_per_traj, (size_t)s.B * 8) : 0;
     const size_t o_ro = !run_off.empty() ? hc.in(run_off.data(), run_off.size() * 8) : 0;
@@ -1206,9 +1392,9 @@ int csp_minsnap_generate_batch(const csp_minsnap_desc *desc, const void *waypoin
     const size_t o_md = hc.out(max_dev, (size_t)s.B * 8), o_vw = hc.out(vel_zero_weight_out, (size_t)s.B * 8);
     const size_t o_it = hc.out(iterations, (size_t)s.B * 4), o_st = hc.out(status, (size_t)s.B * 4);
     const size_t o_sm_out = two_step ? 0 : hc.out(samples, n_sm);
-    const size_t o_tm_out = times ? hc.out(times, n_tm) : 0, o_co_out = coeffs ? hc.out(coeffs, n_co) : 0;
+    const size_t o_tm_out = times ? hc.out(times, z.tm) : 0, o_co_out = coeffs ? hc.out(coeffs, z.co) : 0;
     const size_t o_sm = two_step ? hc.scratch(n_sm) : o_sm_out;
-    const size_t o_tm = times ? o_tm_out : hc.scratch(n_tm), o_co = coeffs ? o_co_out : hc.scratch(n_co);
+    const size_t o_tm = times ? o_tm_out : hc.scratch(z.tm), o_co = coeffs ? o_co_out : hc.scratch(z.co);
     const size_t o_ws = hc.scratch(n_ws);
     const size_t o_tmp = !run_off.empty() ? hc.scratch((size_t)run_off.back() * 24) : 0;
     const size_t o_sc = !run_off.empty() ? hc.scratch((size_t)total_seg * 4) : 0;
@@ -1251,53 +1437,6 @@ int csp_minsnap_generate_batch(const csp_minsnap_desc *desc, const void *waypoin
 
 void csp_minsnap_release_cached_memory(void) { csp::arena_free_idle(); }
 
-}  // extern "C"
-
-namespace {
-
-// csp_minsnap_solve_batch_vjp's own limits on top of validate(): no path penalty (t* is a discrete arg-max and the
-// penalty's chord point depends on T), orders 2..5, trajectory-major coefficients, fp64 arithmetic.
-int validate_vjp(const csp_minsnap_desc *d, Shape &s) {
-    int rc = validate(d, s);
-    if (rc != CSP_OK) return rc;
-    if (d->order < 2) return CSP_ERR_UNSUPPORTED;
-    if (d->path_weight != 0.0) return CSP_ERR_UNSUPPORTED;
-    if (d->flags & (CSP_FLAG_SEGMENT_MAJOR | CSP_FLAG_F32_ARITH)) return CSP_ERR_UNSUPPORTED;
-    return CSP_OK;
-}
-
-size_t vjp_ws_bytes(const csp_minsnap_desc *d, const Shape &s, size_t *part_off) {
-    const size_t factors = align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::vjp_ws_entries(s.order) * (size_t)s.B * 8, 256);
-    if (part_off) *part_off = factors;
-    return factors + (d->bc_per_trajectory ? 0 : 12 * (size_t)csp::vjp_blocks(s.B) * 8);
-}
-
-int dispatch_vjp(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const void *bc, const void *gco,
-                 void *gwp, void *gtm, void *gbc, int32_t *status, const int64_t *seg_off, const double *vw_per, void *ws,
-                 size_t ws_size, hipStream_t st) {
-    size_t part_off = 0;
-    const size_t need = vjp_ws_bytes(d, s, &part_off);
-    if (need > 0 && (!ws || ws_size < need)) return CSP_ERR_WORKSPACE;
-    if ((uintptr_t)ws & 7u) return CSP_ERR_WORKSPACE;
-    if ((uintptr_t)gco & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // p_bar records are read as 2-element vectors
-    csp::VjpArgs a;
-    a.wp = wp; a.times = tm; a.bc = bc; a.grad_coeffs = gco;
-    a.grad_wp = gwp; a.grad_times = gtm; a.grad_bc = gbc; a.status = status;
-    a.seg_off = s.ragged ? seg_off : nullptr;
-    a.ws = ws;
-    a.bc_part = (gbc && !d->bc_per_trajectory) ? (void *)((char *)ws + part_off) : nullptr;
-    a.vw_per = vw_per;
-    a.vel_zero_weight = d->vel_zero_weight;
-    a.B = s.B; a.S = s.S; a.order = s.order; a.bc_per_traj = d->bc_per_trajectory ? 1 : 0;
-    hipError_t e = csp::launch_vjp(a, s.f32, st);
-    if (e != hipSuccess) return hip_fail(e, "vjp kernel launch");
-    return CSP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 size_t csp_minsnap_vjp_workspace_bytes(const csp_minsnap_desc *desc) {
     Shape s;
     if (validate_vjp(desc, s) != CSP_OK) return 0;
@@ -1322,124 +1461,17 @@ int csp_minsnap_solve_batch_vjp(const csp_minsnap_desc *desc, const void *waypoi
                             desc->seg_offsets, desc->vel_zero_weight_per_traj, workspace, workspace_bytes, st);
 
     // CSP_MEM_HOST: staged through the cached arena, synchronous (as csp_minsnap_solve_batch)
-    int64_t total_seg;
-    if (s.ragged) {
-        total_seg = desc->seg_offsets[s.B];
-        for (int64_t b = 0; b < s.B; ++b) {
-            const int64_t n = desc->seg_offsets[b + 1] - desc->seg_offsets[b];
-            if (n < 0 || n > s.Smax) return CSP_ERR_INVALID_ARG;
-        }
-    } else {
-        total_seg = s.B * (int64_t)s.S;
-    }
-    const size_t m = 2 * (size_t)s.order;
-    const size_t n_wp = (size_t)(total_seg + s.B) * 3 * s.elt, n_tm = (size_t)total_seg * s.elt;
-    const size_t n_bc = (size_t)(desc->bc_per_trajectory ? s.B : 1) * 12 * s.elt;
-    const size_t n_co = (size_t)total_seg * 3 * m * s.elt;
+    if (!offsets_ok(desc, s)) return CSP_ERR_INVALID_ARG;
     const size_t n_ws = vjp_ws_bytes(desc, s, nullptr);
-    csp::HostCall hc(current_device(), st);
-    const size_t o_wp = hc.in(waypoints, n_wp), o_tm = hc.in(times, n_tm), o_bc = hc.in(bc, n_bc);
-    const size_t o_gc = hc.in(grad_coeffs, n_co);
-    const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
-    const size_t o_vw = desc->vel_zero_weight_per_traj ? hc.in(desc->vel_zero_weight_per_traj, (size_t)s.B * 8) : 0;
-    const size_t o_gw = grad_waypoints ? hc.out(grad_waypoints, n_wp) : 0;
-    const size_t o_gt = grad_times ? hc.out(grad_times, n_tm) : 0;
-    const size_t o_gb = grad_bc ? hc.out(grad_bc, n_bc) : 0;
-    const size_t o_st = status ? hc.out(status, (size_t)s.B * 4) : 0;
-    const size_t o_ws = hc.scratch(n_ws);
-    CSP_HIP(hc.upload());
-    rc = dispatch_vjp(desc, s, hc.ptr(o_wp), hc.ptr(o_tm), hc.ptr(o_bc), hc.ptr(o_gc), grad_waypoints ? hc.ptr(o_gw) : nullptr,
-                      grad_times ? hc.ptr(o_gt) : nullptr, grad_bc ? hc.ptr(o_gb) : nullptr,
-                      status ? hc.ptr<int32_t>(o_st) : nullptr, s.ragged ? hc.ptr<const int64_t>(o_so) : nullptr,
-                      desc->vel_zero_weight_per_traj ? hc.ptr<const double>(o_vw) : nullptr, hc.ptr(o_ws), n_ws, st);
-    if (rc != CSP_OK) return rc;
-    CSP_HIP(hc.download());
-    return CSP_OK;
+    Stage g(desc, s, st, waypoints, times, bc);
+    const size_t o_gc = g.in(grad_coeffs, g.z.co);
+    const size_t o_gw = g.out(grad_waypoints, g.z.wp), o_gt = g.out(grad_times, g.z.tm), o_gb = g.out(grad_bc, g.z.bc);
+    const size_t o_st = g.out(status, (size_t)s.B * 4), o_ws = g.hc.scratch(n_ws);
+    return g.run([&] {
+        return dispatch_vjp(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(g.bc), g.ptr(o_gc), g.ptr(o_gw), g.ptr(o_gt), g.ptr(o_gb),
+                            g.ptr<int32_t>(o_st), g.ptr<const int64_t>(g.seg_off), g.ptr<const double>(g.vw_per), g.ptr(o_ws), n_ws, st);
+    });
 }
-
-}  // extern "C"
-
-namespace {
-
-// csp_minsnap_cost_batch / csp_minsnap_optimize_times_batch: the VJP's scope (validate_vjp).
-size_t cost_ws_bytes(const Shape &s) {
-    return align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::timeopt_ws_entries(s.order) * (size_t)s.B * 8, 256);
-}
-
-size_t timeopt_ws_bytes(const Shape &s, size_t *vec_off) {
-    const size_t factors = cost_ws_bytes(s);
-    if (vec_off) *vec_off = factors;
-    return factors + 4 * (size_t)s.Smax * (size_t)s.B * 8;
-}
-
-int validate_timeopt(const csp_minsnap_desc *d, const csp_minsnap_timeopt_params *p, Shape &s) {
-    int rc = validate_vjp(d, s);
-    if (rc != CSP_OK) return rc;
-    if (!p || p->abi_version != CSP_MINSNAP_ABI_VERSION) return CSP_ERR_INVALID_ARG;
-    if (p->mode != CSP_TIMEOPT_FIXED_TOTAL && p->mode != CSP_TIMEOPT_TIME_PENALTY) return CSP_ERR_INVALID_ARG;
-    if (p->mode == CSP_TIMEOPT_TIME_PENALTY && !(p->time_weight > 0.0 && std::isfinite(p->time_weight))) return CSP_ERR_INVALID_ARG;
-    if (!(p->min_time > 0.0 && std::isfinite(p->min_time))) return CSP_ERR_INVALID_ARG;
-    if (!(p->tol >= 0.0) || p->max_iters < 0) return CSP_ERR_INVALID_ARG;
-    return CSP_OK;
-}
-
-// FIXED_TOTAL needs sum_j T_j >= S * min_time for every trajectory: checked on the host when the times are host memory.
-bool totals_feasible(const Shape &s, const int64_t *seg_off, const void *times, double tmin) {
-    for (int64_t b = 0; b < s.B; ++b) {
-        const int64_t s0 = s.ragged ? seg_off[b] : b * (int64_t)s.S, s1 = s.ragged ? seg_off[b + 1] : s0 + s.S;
-        double c = 0.0;
-        for (int64_t j = s0; j < s1; ++j) c += s.f32 ? (double)((const float *)times)[j] : ((const double *)times)[j];
-        if (c < (double)(s1 - s0) * tmin) return false;
-    }
-    return true;
-}
-
-void timeopt_args(const csp_minsnap_desc *d, const Shape &s, csp::TimeOptArgs &a) {
-    a = csp::TimeOptArgs{};
-    a.vel_zero_weight = d->vel_zero_weight;
-    a.B = s.B; a.S = s.S; a.Smax = s.Smax; a.order = s.order; a.bc_per_traj = d->bc_per_trajectory ? 1 : 0;
-}
-
-int dispatch_cost(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const void *bc, double *cost,
-                  void *grad, int32_t *status, const int64_t *seg_off, const double *vw_per, void *ws, size_t ws_size,
-                  hipStream_t st) {
-    const size_t need = cost_ws_bytes(s);
-    if (need > 0 && (!ws || ws_size < need)) return CSP_ERR_WORKSPACE;
-    if ((uintptr_t)ws & 7u) return CSP_ERR_WORKSPACE;
-    csp::TimeOptArgs a;
-    timeopt_args(d, s, a);
-    a.wp = wp; a.times = tm; a.bc = bc; a.cost = cost; a.grad = grad; a.status = status;
-    a.seg_off = s.ragged ? seg_off : nullptr;
-    a.ws = ws; a.vw_per = vw_per;
-    hipError_t e = csp::launch_cost(a, s.f32, st);
-    if (e != hipSuccess) return hip_fail(e, "cost kernel launch");
-    return CSP_OK;
-}
-
-int dispatch_timeopt(const csp_minsnap_desc *d, const csp_minsnap_timeopt_params *p, const Shape &s, const void *wp,
-                     const void *tm, const void *bc, void *tout, void *co, double *obj, int32_t *iters, int32_t *status,
-                     const int64_t *seg_off, const double *vw_per, void *ws, size_t ws_size, hipStream_t st) {
-    size_t vec_off = 0;
-    const size_t need = timeopt_ws_bytes(s, &vec_off);
-    if (!ws || ws_size < need || ((uintptr_t)ws & 7u)) return CSP_ERR_WORKSPACE;
-    csp::TimeOptArgs a;
-    timeopt_args(d, s, a);
-    a.wp = wp; a.times = tm; a.bc = bc; a.times_out = tout; a.objective = obj; a.iterations = iters; a.status = status;
-    a.seg_off = s.ragged ? seg_off : nullptr;
-    a.ws = ws; a.vec = (double *)((char *)ws + vec_off); a.vw_per = vw_per;
-    a.mode = p->mode == CSP_TIMEOPT_FIXED_TOTAL ? csp::CSP_TIMEOPT_FIXED_TOTAL_V : csp::CSP_TIMEOPT_TIME_PENALTY_V;
-    a.time_weight = p->time_weight; a.min_time = p->min_time; a.tol = p->tol; a.max_iters = p->max_iters;
-    hipError_t e = csp::launch_timeopt(a, s.f32, st);
-    if (e != hipSuccess) return hip_fail(e, "time optimiser launch");
-    if (!co) return CSP_OK;
-    // the coefficients are csp_minsnap_solve_batch's at the optimised times; its workspace (0 or the generic kernel's
-    // factors, the same size as ours) is the factor region
-    return dispatch(d, s, wp, tout, bc, co, nullptr, nullptr, seg_off, vw_per, ws, vec_off, st);
-}
-
-}  // namespace
-
-extern "C" {
 
 size_t csp_minsnap_cost_workspace_bytes(const csp_minsnap_desc *desc) {
     Shape s;
@@ -1469,35 +1501,16 @@ int csp_minsnap_cost_batch(const csp_minsnap_desc *desc, const void *waypoints, 
         return dispatch_cost(desc, s, waypoints, times, bc, cost, grad_times, status, desc->seg_offsets,
                              desc->vel_zero_weight_per_traj, workspace, workspace_bytes, st);
 
-    int64_t total_seg;
-    if (s.ragged) {
-        total_seg = desc->seg_offsets[s.B];
-        for (int64_t b = 0; b < s.B; ++b) {
-            const int64_t n = desc->seg_offsets[b + 1] - desc->seg_offsets[b];
-            if (n < 0 || n > s.Smax) return CSP_ERR_INVALID_ARG;
-        }
-    } else {
-        total_seg = s.B * (int64_t)s.S;
-    }
-    const size_t n_wp = (size_t)(total_seg + s.B) * 3 * s.elt, n_tm = (size_t)total_seg * s.elt;
-    const size_t n_bc = (size_t)(desc->bc_per_trajectory ? s.B : 1) * 12 * s.elt;
+    // CSP_MEM_HOST: as csp_minsnap_solve_batch
+    if (!offsets_ok(desc, s)) return CSP_ERR_INVALID_ARG;
     const size_t n_ws = cost_ws_bytes(s);
-    csp::HostCall hc(current_device(), st);
-    const size_t o_wp = hc.in(waypoints, n_wp), o_tm = hc.in(times, n_tm), o_bc = hc.in(bc, n_bc);
-    const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
-    const size_t o_vw = desc->vel_zero_weight_per_traj ? hc.in(desc->vel_zero_weight_per_traj, (size_t)s.B * 8) : 0;
-    const size_t o_c = hc.out(cost, (size_t)s.B * 8);
-    const size_t o_g = grad_times ? hc.out(grad_times, n_tm) : 0;
-    const size_t o_st = status ? hc.out(status, (size_t)s.B * 4) : 0;
-    const size_t o_ws = hc.scratch(n_ws);
-    CSP_HIP(hc.upload());
-    rc = dispatch_cost(desc, s, hc.ptr(o_wp), hc.ptr(o_tm), hc.ptr(o_bc), hc.ptr<double>(o_c),
-                       grad_times ? hc.ptr(o_g) : nullptr, status ? hc.ptr<int32_t>(o_st) : nullptr,
-                       s.ragged ? hc.ptr<const int64_t>(o_so) : nullptr,
-                       desc->vel_zero_weight_per_traj ? hc.ptr<const double>(o_vw) : nullptr, hc.ptr(o_ws), n_ws, st);
-    if (rc != CSP_OK) return rc;
-    CSP_HIP(hc.download());
-    return CSP_OK;
+    Stage g(desc, s, st, waypoints, times, bc);
+    const size_t o_c = g.out(cost, (size_t)s.B * 8), o_g = g.out(grad_times, g.z.tm), o_st = g.out(status, (size_t)s.B * 4);
+    const size_t o_ws = g.hc.scratch(n_ws);
+    return g.run([&] {
+        return dispatch_cost(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(g.bc), g.ptr<double>(o_c), g.ptr(o_g), g.ptr<int32_t>(o_st),
+                             g.ptr<const int64_t>(g.seg_off), g.ptr<const double>(g.vw_per), g.ptr(o_ws), n_ws, st);
+    });
 }
 
 int csp_minsnap_optimize_times_batch(const csp_minsnap_desc *desc, const csp_minsnap_timeopt_params *prm,
@@ -1509,12 +1522,8 @@ int csp_minsnap_optimize_times_batch(const csp_minsnap_desc *desc, const csp_min
     if (rc != CSP_OK) return rc;
     if (s.B == 0) return CSP_OK;
     if (!waypoints || !times_in || !bc || !times_out) return CSP_ERR_INVALID_ARG;
-    if (desc->mem_space == CSP_MEM_HOST) {
-        if (s.ragged)
-            for (int64_t b = 0; b < s.B; ++b) {
-                const int64_t n = desc->seg_offsets[b + 1] - desc->seg_offsets[b];
-                if (n < 0 || n > s.Smax) return CSP_ERR_INVALID_ARG;
-            }
+    if (desc->mem_space == CSP_MEM_HOST) {   // the caller's arrays can be read here: checked before a device is looked for
+        if (!offsets_ok(desc, s)) return CSP_ERR_INVALID_ARG;
         if (prm->mode == CSP_TIMEOPT_FIXED_TOTAL && !totals_feasible(s, desc->seg_offsets, times_in, prm->min_time))
             return CSP_ERR_INVALID_ARG;
     }
@@ -1526,57 +1535,17 @@ int csp_minsnap_optimize_times_batch(const csp_minsnap_desc *desc, const csp_min
         return dispatch_timeopt(desc, prm, s, waypoints, times_in, bc, times_out, coeffs, objective, iterations, status,
                                 desc->seg_offsets, desc->vel_zero_weight_per_traj, workspace, workspace_bytes, st);
 
-    const int64_t total_seg = s.ragged ? desc->seg_offsets[s.B] : s.B * (int64_t)s.S;
-    const size_t m = 2 * (size_t)s.order;
-    const size_t n_wp = (size_t)(total_seg + s.B) * 3 * s.elt, n_tm = (size_t)total_seg * s.elt;
-    const size_t n_bc = (size_t)(desc->bc_per_trajectory ? s.B : 1) * 12 * s.elt;
-    const size_t n_co = (size_t)total_seg * 3 * m * s.elt;
+    // CSP_MEM_HOST: as csp_minsnap_solve_batch
     const size_t n_ws = timeopt_ws_bytes(s, nullptr);
-    csp::HostCall hc(current_device(), st);
-    const size_t o_wp = hc.in(waypoints, n_wp), o_tm = hc.in(times_in, n_tm), o_bc = hc.in(bc, n_bc);
-    const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
-    const size_t o_vw = desc->vel_zero_weight_per_traj ? hc.in(desc->vel_zero_weight_per_traj, (size_t)s.B * 8) : 0;
-    const size_t o_to = hc.out(times_out, n_tm);
-    const size_t o_co = coeffs ? hc.out(coeffs, n_co) : 0;
-    const size_t o_ob = objective ? hc.out(objective, (size_t)s.B * 16) : 0;
-    const size_t o_it = iterations ? hc.out(iterations, (size_t)s.B * 4) : 0;
-    const size_t o_st = status ? hc.out(status, (size_t)s.B * 4) : 0;
-    const size_t o_ws = hc.scratch(n_ws);
-    CSP_HIP(hc.upload());
-    rc = dispatch_timeopt(desc, prm, s, hc.ptr(o_wp), hc.ptr(o_tm), hc.ptr(o_bc), hc.ptr(o_to), coeffs ? hc.ptr(o_co) : nullptr,
-                          objective ? hc.ptr<double>(o_ob) : nullptr, iterations ? hc.ptr<int32_t>(o_it) : nullptr,
-                          status ? hc.ptr<int32_t>(o_st) : nullptr, s.ragged ? hc.ptr<const int64_t>(o_so) : nullptr,
-                          desc->vel_zero_weight_per_traj ? hc.ptr<const double>(o_vw) : nullptr, hc.ptr(o_ws), n_ws, st);
-    if (rc != CSP_OK) return rc;
-    CSP_HIP(hc.download());
-    return CSP_OK;
+    Stage g(desc, s, st, waypoints, times_in, bc);
+    const size_t o_to = g.out(times_out, g.z.tm), o_co = g.out(coeffs, g.z.co), o_ob = g.out(objective, (size_t)s.B * 16);
+    const size_t o_it = g.out(iterations, (size_t)s.B * 4), o_st = g.out(status, (size_t)s.B * 4), o_ws = g.hc.scratch(n_ws);
+    return g.run([&] {
+        return dispatch_timeopt(desc, prm, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(g.bc), g.ptr(o_to), g.ptr(o_co), g.ptr<double>(o_ob),
+                                g.ptr<int32_t>(o_it), g.ptr<int32_t>(o_st), g.ptr<const int64_t>(g.seg_off),
+                                g.ptr<const double>(g.vw_per), g.ptr(o_ws), n_ws, st);
+    });
 }
-
-}  // extern "C"
-
-namespace {
-
-// csp_minsnap_solve_periodic_batch: the VJP's scope (validate_vjp); bc_per_trajectory is ignored (there is no bc).
-size_t periodic_ws_bytes(const Shape &s) {
-    return align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::periodic_ws_entries(s.order) * (size_t)s.B * 8, 256);
-}
-
-int dispatch_periodic(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, void *co, double *cost,
-                      void *grad, int32_t *status, const int64_t *seg_off, const double *vw_per, void *ws, hipStream_t st) {
-    csp::PeriodicArgs a{};
-    a.wp = wp; a.times = tm; a.coeffs = co; a.cost = cost; a.grad = grad; a.status = status;
-    a.seg_off = s.ragged ? seg_off : nullptr;
-    a.ws = ws; a.vw_per = vw_per;
-    a.vel_zero_weight = d->vel_zero_weight;
-    a.B = s.B; a.S = s.S; a.order = s.order;
-    hipError_t e = csp::launch_periodic(a, s.f32, st);
-    if (e != hipSuccess) return hip_fail(e, "periodic kernel launch");
-    return CSP_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 size_t csp_minsnap_periodic_workspace_bytes(const csp_minsnap_desc *desc) {
     Shape s;
@@ -1597,11 +1566,8 @@ int csp_minsnap_solve_periodic_batch(const csp_minsnap_desc *desc, const void *w
         if (n_ws > 0 && (!workspace || workspace_bytes < n_ws)) return CSP_ERR_WORKSPACE;
         if ((uintptr_t)workspace & 7u) return CSP_ERR_WORKSPACE;
         if ((uintptr_t)coeffs & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // records are stored as 2-element vectors
-    } else if (s.ragged) {
-        for (int64_t b = 0; b < s.B; ++b) {
-            const int64_t n = desc->seg_offsets[b + 1] - desc->seg_offsets[b];
-            if (n < 0 || n > s.Smax) return CSP_ERR_INVALID_ARG;
-        }
+    } else if (!offsets_ok(desc, s)) {
+        return CSP_ERR_INVALID_ARG;
     }
     rc = select_device(desc->device_id);
     if (rc != CSP_OK) return rc;
@@ -1611,27 +1577,14 @@ int csp_minsnap_solve_periodic_batch(const csp_minsnap_desc *desc, const void *w
         return dispatch_periodic(desc, s, waypoints, times, coeffs, cost, grad_times, status, desc->seg_offsets,
                                  desc->vel_zero_weight_per_traj, workspace, st);
 
-    const int64_t total_seg = s.ragged ? desc->seg_offsets[s.B] : s.B * (int64_t)s.S;
-    const size_t m = 2 * (size_t)s.order;
-    const size_t n_wp = (size_t)total_seg * 3 * s.elt, n_tm = (size_t)total_seg * s.elt;
-    const size_t n_co = (size_t)total_seg * 3 * m * s.elt;
-    csp::HostCall hc(current_device(), st);
-    const size_t o_wp = hc.in(waypoints, n_wp), o_tm = hc.in(times, n_tm);
-    const size_t o_so = s.ragged ? hc.in(desc->seg_offsets, (size_t)(s.B + 1) * 8) : 0;
-    const size_t o_vw = desc->vel_zero_weight_per_traj ? hc.in(desc->vel_zero_weight_per_traj, (size_t)s.B * 8) : 0;
-    const size_t o_co = hc.out(coeffs, n_co);
-    const size_t o_c = cost ? hc.out(cost, (size_t)s.B * 8) : 0;
-    const size_t o_g = grad_times ? hc.out(grad_times, n_tm) : 0;
-    const size_t o_st = status ? hc.out(status, (size_t)s.B * 4) : 0;
-    const size_t o_ws = hc.scratch(n_ws);
-    CSP_HIP(hc.upload());
-    rc = dispatch_periodic(desc, s, hc.ptr(o_wp), hc.ptr(o_tm), hc.ptr(o_co), cost ? hc.ptr<double>(o_c) : nullptr,
-                           grad_times ? hc.ptr(o_g) : nullptr, status ? hc.ptr<int32_t>(o_st) : nullptr,
-                           s.ragged ? hc.ptr<const int64_t>(o_so) : nullptr,
-                           desc->vel_zero_weight_per_traj ? hc.ptr<const double>(o_vw) : nullptr, hc.ptr(o_ws), st);
-    if (rc != CSP_OK) return rc;
-    CSP_HIP(hc.download());
-    return CSP_OK;
+    // CSP_MEM_HOST: as csp_minsnap_solve_batch, S waypoints per trajectory and no bc
+    Stage g(desc, s, st, waypoints, times, nullptr);
+    const size_t o_co = g.out(coeffs, g.z.co), o_c = g.out(cost, (size_t)s.B * 8), o_g = g.out(grad_times, g.z.tm);
+    const size_t o_st = g.out(status, (size_t)s.B * 4), o_ws = g.hc.scratch(n_ws);
+    return g.run([&] {
+        return dispatch_periodic(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(o_co), g.ptr<double>(o_c), g.ptr(o_g), g.ptr<int32_t>(o_st),
+                                 g.ptr<const int64_t>(g.seg_off), g.ptr<const double>(g.vw_per), g.ptr(o_ws), st);
+    });
 }
 
 }  // extern "C"

@@ -113,6 +113,35 @@ def test_no_cpu_fallback(csp):
     assert e.value.code == -5
 
 
+def _capi_contract():
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "capi_contract.json")) as f:
+        return json.load(f)
+
+
+def test_recorded_dispatch_table(csp):
+    """Kernel name and every workspace size of the recorded descriptors (oracle/gen_capi_contract.py, table A): which
+    kernel a descriptor gets, and what it needs, is part of the ABI's behaviour and does not move by accident."""
+    from oracle import gen_capi_contract as gen
+    table = _capi_contract()["dispatch"]
+    n_in = len(gen.DISPATCH_COLUMNS)
+    assert table["columns"][:n_in] == list(gen.DISPATCH_COLUMNS) and len(table["rows"]) >= 250
+    for row in table["rows"]:
+        assert gen.replay_dispatch_row(csp, row[:n_in]) == row[n_in:], dict(zip(table["columns"], row))
+
+
+def test_recorded_return_codes_without_a_device(csp):
+    """The return code of every recorded call that ends before device work (table B): the five staged entries' checks
+    and their order, the device selection included -- a call that passes them all returns CSP_ERR_NO_DEVICE here."""
+    if csp.device_count() > 0:
+        pytest.skip("a device is present; this test is for the CPU-only container")
+    from oracle import gen_capi_contract as gen
+    cases = _capi_contract()["return_codes"]
+    assert {c["entry"] for c in cases} == set(gen.ENTRIES) and len(cases) >= 150
+    for c in cases:
+        assert gen.run_return_code_case(csp, c) == c["rc"], (c["entry"], c["case"])
+
+
 def test_product_code_never_touches_the_oracle():
     """The oracle is test infrastructure: nothing under cs-pathplan_amd/ may import or link it."""
     pkg = os.path.join(ROOT, "cs-pathplan_amd")

@@ -106,7 +106,7 @@ def test_span_kernel_ragged_against_the_long_double_reference(csp, order):
 @pytest.mark.parametrize("S", [17, 24, 32, 33, 48, 64])
 def test_order_5_on_both_sides_of_the_span_switch(csp, S):
     """Order 5 from 17 segments goes to the span kernel once the batch fills a wave per SIMD with span lanes
-    (B << span_lanes_log2(S) >= 65536, minsnap_capi.hip: use_span); one trajectory fewer stays on the chunked kernel."""
+    (B << span_lanes_log2(S) >= 65536, minsnap_capi.hip: pick_kernel); one trajectory fewer stays on the chunked kernel."""
     lanes_log2 = (S - 1).bit_length() - 4          # span_lanes_log2: 16 segments per lane, rounded up to a power of two
     B_span = 65536 >> lanes_log2
     wp, tm, bc, vw = _inputs(B_span, S, 5, 3000 + S)
@@ -321,6 +321,92 @@ def test_mixed_entry_over_long_trajectories_in_both_forms(csp, oracle_mod):
             # the dense oracle's gates of tests/test_gpu_round3.py (measured here: 2.4e-10 per power)
             _gates(blk[:6 * o * n].reshape(n, 3, 2 * o), ref, 1e-6 if o == 5 else 5e-8, ("mixed skip", i, o, n))
     assert np.array_equal(h.coeffs, out_d)
+
+
+# The five entries that stage host memory the same way: C symbol, workspace function, and per pointer argument
+# (name, "in" / "out", required).  Shapes and element types are in _staged_buffers.
+_STAGED = {
+    "solve_batch": ("csp_minsnap_solve_batch", "csp_minsnap_workspace_bytes",
+                    (("waypoints", "in", True), ("times", "in", True), ("bc", "in", True), ("coeffs", "out", True),
+                     ("max_dev", "out", False), ("status", "out", False))),
+    "solve_batch_vjp": ("csp_minsnap_solve_batch_vjp", "csp_minsnap_vjp_workspace_bytes",
+                        (("waypoints", "in", True), ("times", "in", True), ("bc", "in", True), ("grad_coeffs", "in", True),
+                         ("grad_waypoints", "out", False), ("grad_times", "out", False), ("grad_bc", "out", False),
+                         ("status", "out", False))),
+    "cost_batch": ("csp_minsnap_cost_batch", "csp_minsnap_cost_workspace_bytes",
+                   (("waypoints", "in", True), ("times", "in", True), ("bc", "in", True), ("cost", "out", True),
+                    ("grad_times", "out", False), ("status", "out", False))),
+    "optimize_times_batch": ("csp_minsnap_optimize_times_batch", "csp_minsnap_timeopt_workspace_bytes",
+                             (("waypoints", "in", True), ("times", "in", True), ("bc", "in", True), ("times_out", "out", True),
+                              ("coeffs", "out", False), ("objective", "out", False), ("iterations", "out", False),
+                              ("status", "out", False))),
+    "solve_periodic_batch": ("csp_minsnap_solve_periodic_batch", "csp_minsnap_periodic_workspace_bytes",
+                             (("waypoints", "in", True), ("times", "in", True), ("coeffs", "out", True), ("cost", "out", False),
+                              ("grad_times", "out", False), ("status", "out", False))),
+}
+
+
+def _staged_buffers(entry, lens, order, f32, bc_per, seed):
+    """Host arrays of every pointer argument of `entry` for trajectories of `lens` segments (outputs zeroed)."""
+    rng = np.random.default_rng(seed)
+    io = np.float32 if f32 else np.float64
+    B, total, m = len(lens), int(np.sum(lens)), 2 * order
+    n_wp = total if entry == "solve_periodic_batch" else total + B   # a closed loop has no repeated end point
+    b = dict(waypoints=np.cumsum(rng.normal(size=(n_wp, 3)), axis=0).astype(io), times=rng.uniform(0.5, 2.0, size=total).astype(io),
+             bc=rng.normal(size=(B if bc_per else 1, 4, 3)).astype(io), grad_coeffs=rng.normal(size=(total, 3, m)).astype(io))
+    b.update(coeffs=np.zeros((total, 3, m), io), grad_waypoints=np.zeros((n_wp, 3), io), grad_times=np.zeros(total, io),
+             grad_bc=np.zeros_like(b["bc"]), times_out=np.zeros(total, io), max_dev=np.zeros(B), cost=np.zeros(B),
+             objective=np.zeros((B, 2)), status=np.zeros(B, np.int32), iterations=np.zeros(B, np.int32))
+    return b
+
+
+@pytest.mark.parametrize("entry", sorted(_STAGED))
+def test_host_and_device_memory_calls_are_bit_equal(csp, entry):
+    """The host-memory form of an entry is its device-memory form behind a staging copy: the same inputs give the same
+    bits in every output.  Smallest shapes at which the staging can go wrong: a uniform batch of one full 64-trajectory
+    slice plus one (B = 65, S = 3) and a ragged one of lengths (1, 2, 5); every optional output absent and present;
+    shared and per-trajectory bc; with and without per-trajectory weights; orders 2 and 4; fp64 and one fp32-storage
+    case."""
+    import ctypes
+    import torch
+    sym, ws_fn, args = _STAGED[entry]
+    lib = csp.raw_lib()
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    combos = [(order, False, lens, opt, bc_per, vw_per) for order in (2, 4) for lens in ((3,) * 65, (1, 2, 5))
+              for opt in (False, True) for bc_per in (False, True) for vw_per in (False, True)]
+    combos += [(4, True, (3,) * 65, True, True, True), (2, True, (1, 2, 5), True, False, True)]
+    for k, (order, f32, lens, opt, bc_per, vw_per) in enumerate(combos):
+        tag = (entry, order, "f32" if f32 else "f64", len(lens), opt, bc_per, vw_per)
+        ragged = len(lens) == 3
+        B = len(lens)
+        host = _staged_buffers(entry, lens, order, f32, bc_per, 7000 + k)
+        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        vw = np.random.default_rng(k).uniform(0.0, 0.3, size=B)
+        dev = {n: torch.from_numpy(host[n]).cuda() for n, _, _ in args}
+        d_off, d_vw = torch.from_numpy(off).cuda(), torch.from_numpy(vw).cuda()
+        prm = csp.make_timeopt_params(csp.TIMEOPT_FIXED_TOTAL, min_time=0.01, tol=1e-6, max_iters=20)
+        got = {}
+        for form in ("host", "device"):
+            ptr = (lambda n: host[n].ctypes.data) if form == "host" else (lambda n: dev[n].data_ptr())
+            desc = csp.make_desc(order, B, 0 if ragged else lens[0], csp.DTYPE_F32 if f32 else csp.DTYPE_F64, 0.0, 0.02,
+                                 csp.MEM_HOST if form == "host" else csp.MEM_DEVICE, bc_per,
+                                 (off.ctypes.data if form == "host" else d_off.data_ptr()) if ragged else None,
+                                 max(lens) if ragged else 0,
+                                 (vw.ctypes.data if form == "host" else d_vw.data_ptr()) if vw_per else None)
+            call = [ctypes.byref(desc)] + ([ctypes.byref(prm)] if entry == "optimize_times_batch" else [])
+            call += [ptr(n) if (req or opt) else None for n, _, req in args]
+            need = int(getattr(lib, ws_fn)(ctypes.byref(desc)))
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device="cuda") if form == "device" else None
+            rc = getattr(lib, sym)(*call, ws.data_ptr() if ws is not None else None, need if ws is not None else 0, stream)
+            assert rc == 0, (tag, form, rc, csp.strerror(rc))
+            torch.cuda.synchronize()
+            got[form] = {n: (host[n] if form == "host" else dev[n].cpu().numpy()) for n, kind, req in args
+                         if kind == "out" and (req or opt)}
+        # nothing failed (the optimiser may stop at max_iters: CSP_TRAJ_NOT_CONVERGED), so every output element was written;
+        # the VJP without its optional outputs has none to compare: both forms returned CSP_OK
+        assert not (got["host"].get("status", np.zeros(1, np.int32)) & ~csp.TRAJ_NOT_CONVERGED).any(), tag
+        for n in got["host"]:
+            assert got["host"][n].tobytes() == got["device"][n].tobytes(), (tag, n)
 
 
 def _alt_problems(lens, seed):

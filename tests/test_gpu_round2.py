@@ -313,7 +313,7 @@ def test_host_calls_from_several_threads(csp):
 
 def test_sharded_entry_pins_the_kernel_choice(csp):
     """An order-5 batch of 17+ segments picks the span kernel only when the WHOLE batch has >= 65536 span lanes
-    (minsnap_capi.hip use_span); the sharded entry must make that choice once for all chunks.  On this one-GPU box
+    (minsnap_capi.hip pick_kernel); the sharded entry must make that choice once for all chunks.  On this one-GPU box
     the chunk IS the batch, so the check is that the sharded call reports / reproduces the plain call bit for bit
     at both sides of the threshold."""
     n = csp.device_count()
