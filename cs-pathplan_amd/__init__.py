@@ -12,6 +12,8 @@ There is NO CPU fallback: importing fails loudly when the HIP extension has not 
 and every solve call raises when no gfx950 device is visible.
 """
 import ctypes
+import math
+import operator
 import os
 
 import numpy as np
@@ -99,71 +101,61 @@ def make_timeopt_params(mode=TIMEOPT_FIXED_TOTAL, time_weight=0.0, min_time=0.01
     return p
 
 
+class AltParams(ctypes.Structure):
+    """Mirror of `csp_alt_params` (include/csp_alt.h; reference AltitudeParams, uavPathPlanning.hpp:415-421)."""
+    _fields_ = [("lambda_smooth", ctypes.c_double), ("lambda_follow", ctypes.c_double),
+                ("safe_distance", ctypes.c_double), ("max_climb_rate", ctypes.c_double)]
+
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         "cs-pathplan_amd: %s is missing.  Build the HIP extension first "
         "(python cs-pathplan_amd/build.py, or __graft_entry__.build()); there is no CPU fallback." % LIB_PATH)
 
 _lib = ctypes.CDLL(LIB_PATH)
-_lib.csp_minsnap_solve_batch.restype = ctypes.c_int
-_lib.csp_minsnap_solve_batch.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]
-_lib.csp_minsnap_solve_batch_vjp.restype = ctypes.c_int
-_lib.csp_minsnap_solve_batch_vjp.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 9 + [ctypes.c_size_t, ctypes.c_void_p]
-_lib.csp_minsnap_vjp_workspace_bytes.restype = ctypes.c_size_t
-_lib.csp_minsnap_vjp_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
-_lib.csp_minsnap_cost_batch.restype = ctypes.c_int
-_lib.csp_minsnap_cost_batch.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]
-_lib.csp_minsnap_cost_workspace_bytes.restype = ctypes.c_size_t
-_lib.csp_minsnap_cost_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
-_lib.csp_minsnap_optimize_times_batch.restype = ctypes.c_int
-_lib.csp_minsnap_optimize_times_batch.argtypes = ([ctypes.POINTER(Desc), ctypes.POINTER(TimeOptParams)] + [ctypes.c_void_p] * 9
-                                                  + [ctypes.c_size_t, ctypes.c_void_p])
-_lib.csp_minsnap_timeopt_workspace_bytes.restype = ctypes.c_size_t
-_lib.csp_minsnap_timeopt_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
-_lib.csp_minsnap_solve_periodic_batch.restype = ctypes.c_int
-_lib.csp_minsnap_solve_periodic_batch.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 7 + [ctypes.c_size_t, ctypes.c_void_p]
-_lib.csp_minsnap_periodic_workspace_bytes.restype = ctypes.c_size_t
-_lib.csp_minsnap_periodic_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
-_lib.csp_minsnap_solve_batch_sharded.restype = ctypes.c_int
-_lib.csp_minsnap_solve_batch_sharded.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 6 + [ctypes.c_int]
-_lib.csp_minsnap_workspace_bytes.restype = ctypes.c_size_t
-_lib.csp_minsnap_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
-_lib.csp_minsnap_solve_multi.restype = ctypes.c_int
-_lib.csp_minsnap_solve_multi.argtypes = [ctypes.POINTER(Desc), ctypes.c_int] + [ctypes.c_void_p] * 7
-_lib.csp_minsnap_solve_mixed.restype = ctypes.c_int
-_lib.csp_minsnap_solve_mixed.argtypes = [ctypes.POINTER(Desc)] + [ctypes.c_void_p] * 8 + [ctypes.c_size_t, ctypes.c_void_p]
-_lib.csp_minsnap_mixed_workspace_bytes.restype = ctypes.c_size_t
-_lib.csp_minsnap_mixed_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
-_lib.csp_minsnap_time_alloc_batch.restype = ctypes.c_int
-_lib.csp_minsnap_time_alloc_batch.argtypes = [ctypes.POINTER(Desc), ctypes.c_void_p, ctypes.c_double,
-                                              ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
-_lib.csp_minsnap_plan_batch.restype = ctypes.c_int
-_lib.csp_minsnap_plan_batch.argtypes = [ctypes.POINTER(Desc), ctypes.c_void_p, ctypes.c_double, ctypes.c_double] + \
-    [ctypes.c_void_p] * 8 + [ctypes.c_size_t, ctypes.c_void_p]
-_lib.csp_minsnap_plan_workspace_bytes.restype = ctypes.c_size_t
-_lib.csp_minsnap_plan_workspace_bytes.argtypes = [ctypes.POINTER(Desc)]
-_lib.csp_minsnap_sample_batch.restype = ctypes.c_int
-_lib.csp_minsnap_sample_batch.argtypes = [ctypes.POINTER(Desc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
-                                          ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-_lib.csp_minsnap_generate_batch.restype = ctypes.c_int
-_lib.csp_minsnap_generate_batch.argtypes = [ctypes.POINTER(Desc), ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
-                                            ctypes.c_double, ctypes.c_int64] + [ctypes.c_void_p] * 10 + [ctypes.c_size_t, ctypes.c_void_p]
-_lib.csp_minsnap_sample_capacity.restype = ctypes.c_int64
-_lib.csp_minsnap_sample_capacity.argtypes = [ctypes.POINTER(Desc), ctypes.c_void_p, ctypes.c_double, ctypes.c_double]
-for _n in ("csp_geo_wgs84_to_enu_batch", "csp_geo_enu_to_wgs84_batch"):
-    getattr(_lib, _n).restype = ctypes.c_int
-    getattr(_lib, _n).argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32,
-                                  ctypes.c_int32, ctypes.c_void_p]
-_lib.csp_minsnap_kernel_name.restype = ctypes.c_char_p
-_lib.csp_minsnap_kernel_name.argtypes = [ctypes.POINTER(Desc)]
-_lib.csp_minsnap_device_count.restype = ctypes.c_int
-_lib.csp_minsnap_version.restype = ctypes.c_char_p
-_lib.csp_minsnap_strerror.restype = ctypes.c_char_p
-_lib.csp_minsnap_strerror.argtypes = [ctypes.c_int]
-_lib.csp_minsnap_last_hip_error.restype = ctypes.c_char_p
 
-
-_lib.csp_minsnap_release_cached_memory.restype = None
+# every prototype of the library: symbol -> (restype, argtypes)
+_I, _I32, _I64, _U32, _SZ, _F, _P, _S = (ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_size_t,
+                                         ctypes.c_double, ctypes.c_void_p, ctypes.c_char_p)
+_D, _ALT = ctypes.POINTER(Desc), ctypes.POINTER(AltParams)
+_PROTOTYPES = {
+    "csp_minsnap_solve_batch": (_I, [_D] + [_P] * 7 + [_SZ, _P]),
+    "csp_minsnap_solve_batch_sharded": (_I, [_D] + [_P] * 6 + [_I]),
+    "csp_minsnap_workspace_bytes": (_SZ, [_D]),
+    "csp_minsnap_solve_batch_vjp": (_I, [_D] + [_P] * 9 + [_SZ, _P]),
+    "csp_minsnap_vjp_workspace_bytes": (_SZ, [_D]),
+    "csp_minsnap_cost_batch": (_I, [_D] + [_P] * 7 + [_SZ, _P]),
+    "csp_minsnap_cost_workspace_bytes": (_SZ, [_D]),
+    "csp_minsnap_optimize_times_batch": (_I, [_D, ctypes.POINTER(TimeOptParams)] + [_P] * 9 + [_SZ, _P]),
+    "csp_minsnap_timeopt_workspace_bytes": (_SZ, [_D]),
+    "csp_minsnap_solve_periodic_batch": (_I, [_D] + [_P] * 7 + [_SZ, _P]),
+    "csp_minsnap_periodic_workspace_bytes": (_SZ, [_D]),
+    "csp_minsnap_solve_multi": (_I, [_D, _I] + [_P] * 7),
+    "csp_minsnap_solve_mixed": (_I, [_D] + [_P] * 8 + [_SZ, _P]),
+    "csp_minsnap_mixed_workspace_bytes": (_SZ, [_D]),
+    "csp_minsnap_time_alloc_batch": (_I, [_D, _P, _F, _F, _P, _P]),
+    "csp_minsnap_plan_batch": (_I, [_D, _P, _F, _F] + [_P] * 8 + [_SZ, _P]),
+    "csp_minsnap_plan_workspace_bytes": (_SZ, [_D]),
+    "csp_minsnap_sample_batch": (_I, [_D, _P, _P, _F, _I64, _P, _P, _P, _P]),
+    "csp_minsnap_generate_batch": (_I, [_D, _P, _F, _F, _P, _F, _I64] + [_P] * 10 + [_SZ, _P]),
+    "csp_minsnap_sample_capacity": (_I64, [_D, _P, _F, _F]),
+    "csp_minsnap_kernel_name": (_S, [_D]),
+    "csp_minsnap_device_count": (_I, None),
+    "csp_minsnap_version": (_S, None),
+    "csp_minsnap_strerror": (_S, [_I]),
+    "csp_minsnap_last_hip_error": (_S, None),
+    "csp_minsnap_release_cached_memory": (None, None),
+    "csp_geo_wgs84_to_enu_batch": (_I, [_P, _P, _P, _I64, _U32, _I32, _P]),
+    "csp_geo_enu_to_wgs84_batch": (_I, [_P, _P, _P, _I64, _U32, _I32, _P]),
+    "csp_alt_workspace_bytes": (_SZ, [_I64]),
+    "csp_alt_optimize_heights_batch": (_I, [_P, _P, _P, _I64, _ALT, _P, _P, _SZ, _U32, _I32, _P]),
+    "csp_alt_global_smooth_batch": (_I, [_P, _P, _P, _I64, _ALT, _P, _P, _P, _SZ, _U32, _I32, _P]),
+    "csp_bezier_generate_batch": (_I, [_P, _P, _I64, _F, _F, _I64, _P, _P, _U32, _I32, _P]),
+}
+for _n, (_r, _a) in _PROTOTYPES.items():
+    getattr(_lib, _n).restype = _r
+    if _a is not None:
+        getattr(_lib, _n).argtypes = _a
 
 
 def release_cached_memory():
@@ -191,10 +183,6 @@ def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
 
-def _np_dtype(dtype_code):
-    return np.float32 if dtype_code == DTYPE_F32 else np.float64
-
-
 def make_desc(order, batch, num_segments=0, dtype=DTYPE_F64, path_weight=0.0, vel_zero_weight=0.0,
               mem_space=MEM_HOST, bc_per_trajectory=False, seg_offsets_ptr=None, max_segments=0,
               vw_per_ptr=None, device_id=-1, flags=0):
@@ -217,6 +205,12 @@ def make_desc(order, batch, num_segments=0, dtype=DTYPE_F64, path_weight=0.0, ve
     return d
 
 
+def _flags(force_generic=False, segment_major=False, no_persistent=False, f32_arith=False, long_segments=False, span=False):
+    return ((FLAG_FORCE_GENERIC if force_generic else 0) | (FLAG_SEGMENT_MAJOR if segment_major else 0)
+            | (FLAG_NO_PERSISTENT if no_persistent else 0) | (FLAG_F32_ARITH if f32_arith else 0)
+            | (FLAG_LONG_SEGMENTS if long_segments else 0) | (FLAG_SPAN if span else 0))
+
+
 def workspace_bytes(desc):
     return int(_lib.csp_minsnap_workspace_bytes(ctypes.byref(desc)))
 
@@ -229,6 +223,169 @@ def kernel_name(desc):
 def _check(rc):
     if rc != 0:
         raise CspError(rc, _lib.csp_minsnap_last_hip_error().decode() if rc == -4 or rc == -5 else "")
+
+
+# ---- the inputs of a call, in the memory space they arrived in ----
+# A backend is that memory space: numpy arrays -> CSP_MEM_HOST, torch CUDA tensors -> CSP_MEM_DEVICE.  Element kinds are named
+# "f32" / "f64" (kind() of the array that sets the storage dtype), "i32", "i64", "u8"; every entry point below is written
+# once against the backend's contig / ptr / empty / zeros / workspace / stream / sync, mem_space and device_id.
+
+_DTYPE_NAME = {"f32": "float32", "f64": "float64", "i32": "int32", "i64": "int64", "u8": "uint8"}
+_NP_DTYPE = {k: np.dtype(v) for k, v in _DTYPE_NAME.items()}
+_TORCH_DTYPE = {} if torch is None else {k: getattr(torch, v) for k, v in _DTYPE_NAME.items()}
+
+
+class _HostMem:
+    """numpy arrays.  The library stages host-memory calls itself: they take no workspace and no stream."""
+    mem_space, device_id = MEM_HOST, -1
+
+    def kind(self, x):
+        return "f32" if (x if isinstance(x, np.ndarray) else np.asarray(x)).dtype == np.float32 else "f64"
+
+    def contig(self, x, kind):
+        return np.ascontiguousarray(x, dtype=_NP_DTYPE[kind])
+
+    addr = staticmethod(operator.attrgetter("ctypes.data"))   # of an array that is there; ptr() also takes None
+
+    def ptr(self, a):
+        return a.ctypes.data if a is not None else None
+
+    def empty(self, shape, kind):
+        return np.empty(shape, dtype=_NP_DTYPE[kind])
+
+    def zeros(self, shape, kind):
+        return np.zeros(shape, dtype=_NP_DTYPE[kind])
+
+    def workspace(self, need, given=None):
+        return None, 0
+
+    def stream(self, given=None):
+        return None
+
+    def sync(self):
+        pass
+
+
+_HOST = _HostMem()
+
+
+class _DeviceMem:
+    """torch CUDA tensors on the device of `like`; calls are enqueued on the caller's stream or torch's current one."""
+    mem_space = MEM_DEVICE
+
+    def __init__(self, like):
+        if not like.is_cuda:
+            raise ValueError("torch inputs must be CUDA tensors (use numpy arrays for host memory)")
+        self.dev = like.device
+        self.device_id = self.dev.index if self.dev.index is not None else -1
+
+    def kind(self, x):
+        return "f32" if x.dtype == torch.float32 else "f64"
+
+    def contig(self, x, kind):
+        dt = _TORCH_DTYPE[kind]
+        if x.dtype != dt or x.device != self.dev:
+            x = x.to(device=self.dev, dtype=dt)
+        return x.contiguous()
+
+    addr = staticmethod(operator.methodcaller("data_ptr"))
+
+    def ptr(self, t):
+        return t.data_ptr() if t is not None else None
+
+    def empty(self, shape, kind):
+        return torch.empty(shape, dtype=_TORCH_DTYPE[kind], device=self.dev)
+
+    def zeros(self, shape, kind):
+        return torch.zeros(shape, dtype=_TORCH_DTYPE[kind], device=self.dev)
+
+    def workspace(self, need, given=None):
+        """(pointer, bytes) of `need` bytes: the caller's `given` when it is large enough, else a new allocation, which
+        lives as long as this object."""
+        if not need:
+            return None, 0
+        if given is None or given.numel() * given.element_size() < need:
+            given = self._ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        return given.data_ptr(), need
+
+    def stream(self, given=None):
+        return ctypes.c_void_p(given if given is not None else torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def sync(self):
+        torch.cuda.current_stream(self.dev).synchronize()
+
+
+def _mem(x):
+    return _DeviceMem(x) if type(x).__module__.startswith("torch") else _HOST
+
+
+def _dtype_code(kind):
+    return DTYPE_F32 if kind == "f32" else DTYPE_F64
+
+
+def _ragged_dims(mem, seg_offsets, times, max_segments):
+    """(seg_offsets as contiguous int64 or None, B, S, segments in total, max_segments) of uniform times [B,S], or of
+    ragged times [sum S_b] with seg_offsets [B+1] (S = 0; max_segments taken from the offsets when not given)."""
+    if seg_offsets is None:
+        B, S = times.shape
+        return None, B, S, B * S, max_segments
+    off = mem.contig(seg_offsets, "i64")
+    B = off.shape[0] - 1
+    if max_segments is None:
+        max_segments = int((off[1:] - off[:-1]).max()) if B else 1
+    return off, B, 0, math.prod(times.shape), max_segments
+
+
+def _bc_block(mem, bc, kind):
+    """bc as [rows,4,3] in the storage dtype; None = one shared row block of zeros."""
+    return mem.zeros((1, 4, 3), kind) if bc is None else mem.contig(bc, kind).reshape(-1, 4, 3)
+
+
+def _workspace(mem, given, size_fn, *size_args):
+    """(pointer, bytes) of a call's workspace, the caller's `given` where it is large enough.  Only device-memory calls
+    take one, and only they ask for its size."""
+    if mem.mem_space == MEM_HOST:
+        return None, 0
+    return mem.workspace(size_fn(*size_args), given)
+
+
+def _scratch(mem, size_fn, *size_args):
+    """(pointer, bytes) of the workspace of an entry that takes none from its caller (plan, generate, altitude): a device
+    call gets a pointer that is never null, whatever size the library asks for."""
+    if mem.mem_space == MEM_HOST:
+        return None, 0
+    need = size_fn(*size_args)
+    return mem.workspace(max(need, 1))[0], need
+
+
+class _CallInputs:
+    """waypoints / times / bc / seg_offsets / per-trajectory weights of one call, made contiguous in the memory space
+    they came in.  Whether bc rows are per trajectory, and whether their count is checked, is the entry's choice."""
+
+    def __init__(self, waypoints, times, bc=None, seg_offsets=None, max_segments=None, vel_zero_weight_per_traj=None):
+        self.mem = mem = _mem(waypoints)
+        self.io = io = mem.kind(waypoints)
+        self.waypoints, self.times = mem.contig(waypoints, io), mem.contig(times, io)
+        self.seg_offsets, self.B, self.S, self.total, self.max_segments = _ragged_dims(mem, seg_offsets, self.times, max_segments)
+        self.bc = _bc_block(mem, bc, io)
+        self.vwp = None if vel_zero_weight_per_traj is None else mem.contig(vel_zero_weight_per_traj, "f64")
+
+    def checked_bc_per_trajectory(self):
+        if self.bc.shape[0] not in (1, self.B):
+            raise ValueError("bc must be [4,3], [1,4,3] or [B,4,3]")
+        return self.bc.shape[0] == self.B
+
+    def desc(self, order, bc_per_trajectory, path_weight=0.0, vel_zero_weight=0.0, flags=0):
+        mem = self.mem
+        return make_desc(order, self.B, self.S, _dtype_code(self.io), path_weight, vel_zero_weight, mem.mem_space,
+                         bc_per_trajectory, mem.ptr(self.seg_offsets), self.max_segments or 0, mem.ptr(self.vwp),
+                         mem.device_id, flags)
+
+    def coeffs_shape(self, order, segment_major=False):
+        m = 2 * int(order)
+        if self.seg_offsets is not None:
+            return (self.total, 3, m)
+        return (self.S, self.B, 3, m) if segment_major else (self.B, self.S, 3, m)
 
 
 class Result:
@@ -250,110 +407,26 @@ def solve_batch(waypoints, times, bc=None, order=4, path_weight=0.0, vel_zero_we
     with concatenated waypoints [sum(S_b+1),3] and times [sum S_b].
     bc: [4,3] / [1,4,3] shared or [B,4,3] per trajectory; rows start vel, end vel, start acc,
     end acc (reference Vel/Acc); None = zeros (MinimumSnapConfig defaults, minimum_snap.hpp:29-32).
+    ngpu: csp_minsnap_solve_batch_sharded, synchronous, from this one process -- a host batch cut into contiguous chunks
+    over `ngpu` devices, a device batch scattered from / gathered to its (root) device over RCCL.
     Returns Result(coeffs [B,S,3,2o] (ragged: [sum S_b,3,2o]), max_dev, status, kernel name).
     """
-    on_device = _is_torch(waypoints)
-    ragged = seg_offsets is not None
-    flags = ((FLAG_FORCE_GENERIC if force_generic else 0) | (FLAG_SEGMENT_MAJOR if segment_major else 0)
-             | (FLAG_NO_PERSISTENT if no_persistent else 0) | (FLAG_F32_ARITH if f32_arith else 0)
-             | (FLAG_SPAN if span else 0))
-    if segment_major and ragged:
+    if segment_major and seg_offsets is not None:
         raise ValueError("segment_major needs a uniform batch")
-    m = 2 * int(order)
-    if on_device:
-        import torch
-        if not waypoints.is_cuda:
-            raise ValueError("torch inputs must be CUDA tensors (use numpy arrays for host memory)")
-        tdt = waypoints.dtype
-        dtype = DTYPE_F32 if tdt == torch.float32 else DTYPE_F64
-        dev = waypoints.device
-        waypoints, times = waypoints.contiguous(), times.to(tdt).contiguous()
-        if ragged:
-            seg_offsets = seg_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            B = seg_offsets.numel() - 1
-            total = times.numel()
-            if max_segments is None:
-                max_segments = int((seg_offsets[1:] - seg_offsets[:-1]).max().item()) if B else 1
-            S = 0
-        else:
-            B, S = times.shape
-            total = B * S
-        if bc is None:
-            bc = torch.zeros((1, 4, 3), dtype=tdt, device=dev)
-        bc = bc.to(tdt).contiguous().reshape(-1, 4, 3)
-        if bc.shape[0] not in (1, B):
-            raise ValueError("bc must be [4,3], [1,4,3] or [B,4,3]")
-        per = bc.shape[0] == B
-        if out is None:
-            out = torch.empty((total, 3, m) if ragged else ((S, B, 3, m) if segment_major else (B, S, 3, m)), dtype=tdt, device=dev)
-        md = torch.empty(B, dtype=torch.float64, device=dev) if want_max_dev else None
-        stt = torch.empty(B, dtype=torch.int32, device=dev) if want_status else None
-        vwp = None
-        if vel_zero_weight_per_traj is not None:
-            vwp = vel_zero_weight_per_traj.to(device=dev, dtype=torch.float64).contiguous()
-        desc = make_desc(order, B, S, dtype, path_weight, vel_zero_weight, MEM_DEVICE, per,
-                         seg_offsets.data_ptr() if ragged else None, max_segments or 0,
-                         vwp.data_ptr() if vwp is not None else None,
-                         dev.index if dev.index is not None else -1, flags)
-        need = workspace_bytes(desc)
-        if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
-            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        if ngpu is not None:
-            # the batch is resident on THIS (root) device: scatter / solve / gather over RCCL from one process, synchronous
-            # (include/csp_minsnap.h: csp_minsnap_solve_batch_sharded with CSP_MEM_DEVICE)
-            rc = _lib.csp_minsnap_solve_batch_sharded(
-                ctypes.byref(desc), waypoints.data_ptr(), times.data_ptr(), bc.data_ptr(), out.data_ptr(),
-                md.data_ptr() if md is not None else None, stt.data_ptr() if stt is not None else None, int(ngpu))
-            _check(rc)
-            return Result(out, md, stt, kernel_name(desc))
-        rc = _lib.csp_minsnap_solve_batch(
-            ctypes.byref(desc), waypoints.data_ptr(), times.data_ptr(), bc.data_ptr(), out.data_ptr(),
-            md.data_ptr() if md is not None else None, stt.data_ptr() if stt is not None else None,
-            workspace.data_ptr() if need else None, need, ctypes.c_void_p(st))
-        _check(rc)
-        return Result(out, md, stt, kernel_name(desc))
-
-    # host memory
-    waypoints = np.asarray(waypoints)
-    dtype = DTYPE_F32 if waypoints.dtype == np.float32 else DTYPE_F64
-    npdt = _np_dtype(dtype)
-    waypoints = np.ascontiguousarray(waypoints, dtype=npdt)
-    times = np.ascontiguousarray(times, dtype=npdt)
-    if ragged:
-        seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.int64)
-        B = seg_offsets.shape[0] - 1
-        total = times.shape[0]
-        if max_segments is None:
-            max_segments = int(np.max(np.diff(seg_offsets))) if B else 1
-        S = 0
-    else:
-        B, S = times.shape
-        total = B * S
-    bc = np.zeros((1, 4, 3), dtype=npdt) if bc is None else np.ascontiguousarray(bc, dtype=npdt).reshape(-1, 4, 3)
-    if bc.shape[0] not in (1, B):
-        raise ValueError("bc must be [4,3], [1,4,3] or [B,4,3]")
-    per = bc.shape[0] == B
+    ci = _CallInputs(waypoints, times, bc, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    mem, p = ci.mem, ci.mem.ptr
+    desc = ci.desc(order, ci.checked_bc_per_trajectory(), path_weight, vel_zero_weight,
+                   _flags(force_generic, segment_major, no_persistent, f32_arith, span=span))
     if out is None:
-        out = np.empty((total, 3, m) if ragged else ((S, B, 3, m) if segment_major else (B, S, 3, m)), dtype=npdt)
-    md = np.empty(B, dtype=np.float64) if want_max_dev else None
-    stt = np.empty(B, dtype=np.int32) if want_status else None
-    vwp = None
-    if vel_zero_weight_per_traj is not None:
-        vwp = np.ascontiguousarray(vel_zero_weight_per_traj, dtype=np.float64)
-    desc = make_desc(order, B, S, dtype, path_weight, vel_zero_weight, MEM_HOST, per,
-                     seg_offsets.ctypes.data if ragged else None, max_segments or 0,
-                     vwp.ctypes.data if vwp is not None else None, -1, flags)
-    if ngpu is not None:   # one process, the batch cut into contiguous chunks over `ngpu` devices (host arrays only)
-        rc = _lib.csp_minsnap_solve_batch_sharded(
-            ctypes.byref(desc), waypoints.ctypes.data, times.ctypes.data, bc.ctypes.data, out.ctypes.data,
-            md.ctypes.data if md is not None else None, stt.ctypes.data if stt is not None else None, int(ngpu))
+        out = mem.empty(ci.coeffs_shape(order, segment_major), ci.io)
+    md = mem.empty((ci.B,), "f64") if want_max_dev else None
+    stt = mem.empty((ci.B,), "i32") if want_status else None
+    wsp, need = _workspace(mem, workspace, workspace_bytes, desc)
+    args = (ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(ci.bc), p(out), p(md), p(stt))
+    if ngpu is not None:
+        _check(_lib.csp_minsnap_solve_batch_sharded(*args, int(ngpu)))
     else:
-        rc = _lib.csp_minsnap_solve_batch(
-            ctypes.byref(desc), waypoints.ctypes.data, times.ctypes.data, bc.ctypes.data, out.ctypes.data,
-            md.ctypes.data if md is not None else None, stt.ctypes.data if stt is not None else None,
-            None, 0, None)
-    _check(rc)
+        _check(_lib.csp_minsnap_solve_batch(*args, wsp, need, mem.stream(stream)))
     return Result(out, md, stt, kernel_name(desc))
 
 
@@ -384,87 +457,23 @@ def solve_batch_vjp(waypoints, times, grad_coeffs, bc=None, order=4, vel_zero_we
     for w in want:
         if w not in _VJP_WANT:
             raise ValueError("want: a subset of %r" % (_VJP_WANT,))
-    ragged = seg_offsets is not None
-    m = 2 * int(order)
-    if _is_torch(waypoints):
-        import torch
-        if not waypoints.is_cuda:
-            raise ValueError("torch inputs must be CUDA tensors (use numpy arrays for host memory)")
-        tdt = waypoints.dtype
-        dtype = DTYPE_F32 if tdt == torch.float32 else DTYPE_F64
-        dev = waypoints.device
-        waypoints, times = waypoints.contiguous(), times.to(tdt).contiguous()
-        gco = grad_coeffs.to(device=dev, dtype=tdt).contiguous()
-        if gco.data_ptr() % 16:
-            gco = gco.clone()
-        if ragged:
-            seg_offsets = seg_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            B, S, total = seg_offsets.numel() - 1, 0, times.numel()
-            if max_segments is None:
-                max_segments = int((seg_offsets[1:] - seg_offsets[:-1]).max().item()) if B else 1
-        else:
-            B, S = times.shape
-            total = B * S
-        if gco.numel() != total * 3 * m:
-            raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % (total * 3 * m))
-        bc = torch.zeros((1, 4, 3), dtype=tdt, device=dev) if bc is None else bc.to(tdt).contiguous().reshape(-1, 4, 3)
-        if bc.shape[0] not in (1, B):
-            raise ValueError("bc must be [4,3], [1,4,3] or [B,4,3]")
-        per = bc.shape[0] == B
-        gwp = torch.empty_like(waypoints) if "waypoints" in want else None
-        gtm = torch.empty_like(times) if "times" in want else None
-        gbc = torch.empty_like(bc) if "bc" in want else None
-        stt = torch.empty(B, dtype=torch.int32, device=dev) if want_status else None
-        vwp = None
-        if vel_zero_weight_per_traj is not None:
-            vwp = vel_zero_weight_per_traj.to(device=dev, dtype=torch.float64).contiguous()
-        desc = make_desc(order, B, S, dtype, 0.0, vel_zero_weight, MEM_DEVICE, per,
-                         seg_offsets.data_ptr() if ragged else None, max_segments or 0,
-                         vwp.data_ptr() if vwp is not None else None, dev.index if dev.index is not None else -1, 0)
-        need = vjp_workspace_bytes(desc)
-        if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
-            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        _check(_lib.csp_minsnap_solve_batch_vjp(
-            ctypes.byref(desc), waypoints.data_ptr(), times.data_ptr(), bc.data_ptr(), gco.data_ptr(), ptr(gwp), ptr(gtm),
-            ptr(gbc), ptr(stt), workspace.data_ptr() if need else None, need, ctypes.c_void_p(st)))
-        return VjpResult(gwp, gtm, gbc, stt)
-
-    waypoints = np.asarray(waypoints)
-    dtype = DTYPE_F32 if waypoints.dtype == np.float32 else DTYPE_F64
-    npdt = _np_dtype(dtype)
-    waypoints = np.ascontiguousarray(waypoints, dtype=npdt)
-    times = np.ascontiguousarray(times, dtype=npdt)
-    gco = np.ascontiguousarray(grad_coeffs, dtype=npdt)
-    if ragged:
-        seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.int64)
-        B, S, total = seg_offsets.shape[0] - 1, 0, times.shape[0]
-        if max_segments is None:
-            max_segments = int(np.max(np.diff(seg_offsets))) if B else 1
-    else:
-        B, S = times.shape
-        total = B * S
-    if gco.size != total * 3 * m:
-        raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % (total * 3 * m))
-    bc = np.zeros((1, 4, 3), dtype=npdt) if bc is None else np.ascontiguousarray(bc, dtype=npdt).reshape(-1, 4, 3)
-    if bc.shape[0] not in (1, B):
-        raise ValueError("bc must be [4,3], [1,4,3] or [B,4,3]")
-    per = bc.shape[0] == B
-    gwp = np.empty_like(waypoints) if "waypoints" in want else None
-    gtm = np.empty_like(times) if "times" in want else None
-    gbc = np.empty_like(bc) if "bc" in want else None
-    stt = np.empty(B, dtype=np.int32) if want_status else None
-    vwp = None
-    if vel_zero_weight_per_traj is not None:
-        vwp = np.ascontiguousarray(vel_zero_weight_per_traj, dtype=np.float64)
-    desc = make_desc(order, B, S, dtype, 0.0, vel_zero_weight, MEM_HOST, per,
-                     seg_offsets.ctypes.data if ragged else None, max_segments or 0,
-                     vwp.ctypes.data if vwp is not None else None, -1, 0)
-    ptr = lambda a: a.ctypes.data if a is not None else None
-    _check(_lib.csp_minsnap_solve_batch_vjp(
-        ctypes.byref(desc), waypoints.ctypes.data, times.ctypes.data, bc.ctypes.data, gco.ctypes.data, ptr(gwp), ptr(gtm),
-        ptr(gbc), ptr(stt), None, 0, None))
+    ci = _CallInputs(waypoints, times, bc, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    mem, p = ci.mem, ci.mem.ptr
+    gco = mem.contig(grad_coeffs, ci.io)
+    if mem.mem_space == MEM_DEVICE and gco.data_ptr() % 16:   # the kernel reads it in 16-byte pieces (host memory is staged)
+        gco = gco.clone()
+    n = ci.total * 3 * 2 * int(order)
+    if math.prod(gco.shape) != n:
+        raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % n)
+    # B == 1 counts as per trajectory here: the library sizes the workspace and picks the bc reduction from this flag
+    desc = ci.desc(order, ci.checked_bc_per_trajectory(), 0.0, vel_zero_weight)
+    gwp = mem.empty(ci.waypoints.shape, ci.io) if "waypoints" in want else None
+    gtm = mem.empty(ci.times.shape, ci.io) if "times" in want else None
+    gbc = mem.empty(ci.bc.shape, ci.io) if "bc" in want else None
+    stt = mem.empty((ci.B,), "i32") if want_status else None
+    wsp, need = _workspace(mem, workspace, vjp_workspace_bytes, desc)
+    _check(_lib.csp_minsnap_solve_batch_vjp(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(ci.bc), p(gco), p(gwp), p(gtm),
+                                            p(gbc), p(stt), wsp, need, mem.stream(stream)))
     return VjpResult(gwp, gtm, gbc, stt)
 
 
@@ -527,83 +536,6 @@ def timeopt_workspace_bytes(desc):
     return int(_lib.csp_minsnap_timeopt_workspace_bytes(ctypes.byref(desc)))
 
 
-class _CallInputs:
-    """waypoints / times / bc / seg_offsets / per-trajectory weights of one call, made contiguous in the memory space
-    they came in (numpy -> CSP_MEM_HOST, torch CUDA -> CSP_MEM_DEVICE), with the descriptor and an allocator for outputs."""
-
-    def __init__(self, waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj):
-        self.torch = _is_torch(waypoints)
-        ragged = seg_offsets is not None
-        if self.torch:
-            import torch
-            if not waypoints.is_cuda:
-                raise ValueError("torch inputs must be CUDA tensors (use numpy arrays for host memory)")
-            tdt = waypoints.dtype
-            self.dtype = DTYPE_F32 if tdt == torch.float32 else DTYPE_F64
-            self.dev = dev = waypoints.device
-            self.waypoints, self.times = waypoints.contiguous(), times.to(tdt).contiguous()
-            if ragged:
-                seg_offsets = seg_offsets.to(device=dev, dtype=torch.int64).contiguous()
-                B, S = seg_offsets.numel() - 1, 0
-                if max_segments is None:
-                    max_segments = int((seg_offsets[1:] - seg_offsets[:-1]).max().item()) if B else 1
-            else:
-                B, S = self.times.shape
-            bc = torch.zeros((1, 4, 3), dtype=tdt, device=dev) if bc is None else bc.to(tdt).contiguous().reshape(-1, 4, 3)
-            vwp = None
-            if vel_zero_weight_per_traj is not None:
-                vwp = vel_zero_weight_per_traj.to(device=dev, dtype=torch.float64).contiguous()
-            self.ptr = lambda t: t.data_ptr() if t is not None else None
-            mem, dev_id = MEM_DEVICE, dev.index if dev.index is not None else -1
-        else:
-            waypoints = np.asarray(waypoints)
-            self.dtype = DTYPE_F32 if waypoints.dtype == np.float32 else DTYPE_F64
-            npdt = _np_dtype(self.dtype)
-            self.waypoints = np.ascontiguousarray(waypoints, dtype=npdt)
-            self.times = np.ascontiguousarray(times, dtype=npdt)
-            if ragged:
-                seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.int64)
-                B, S = seg_offsets.shape[0] - 1, 0
-                if max_segments is None:
-                    max_segments = int(np.max(np.diff(seg_offsets))) if B else 1
-            else:
-                B, S = self.times.shape
-            bc = np.zeros((1, 4, 3), dtype=npdt) if bc is None else np.ascontiguousarray(bc, dtype=npdt).reshape(-1, 4, 3)
-            vwp = None
-            if vel_zero_weight_per_traj is not None:
-                vwp = np.ascontiguousarray(vel_zero_weight_per_traj, dtype=np.float64)
-            self.ptr = lambda a: a.ctypes.data if a is not None else None
-            mem, dev_id = MEM_HOST, -1
-        if bc.shape[0] not in (1, B):
-            raise ValueError("bc must be [4,3], [1,4,3] or [B,4,3]")
-        self.bc, self.B, self.seg_offsets, self.vwp = bc, B, seg_offsets, vwp
-        self.desc = make_desc(order, B, S, self.dtype, 0.0, vel_zero_weight, mem, bc.shape[0] == B,
-                              self.ptr(seg_offsets) if ragged else None, max_segments or 0, self.ptr(vwp), dev_id, 0)
-
-    def empty(self, shape, kind):
-        """kind: 'io' (the storage dtype), 'f64' or 'i32'."""
-        if self.torch:
-            import torch
-            dt = {"io": self.waypoints.dtype, "f64": torch.float64, "i32": torch.int32}[kind]
-            return torch.empty(shape, dtype=dt, device=self.dev)
-        dt = {"io": _np_dtype(self.dtype), "f64": np.float64, "i32": np.int32}[kind]
-        return np.empty(shape, dtype=dt)
-
-    def workspace(self, need, workspace):
-        if not self.torch or not need:
-            return None, 0
-        import torch
-        if workspace is None or workspace.numel() * workspace.element_size() < need:
-            workspace = torch.empty(need, dtype=torch.uint8, device=self.dev)
-        return workspace.data_ptr(), need
-
-    def stream(self, stream):
-        if not self.torch:
-            return None
-        import torch
-        return ctypes.c_void_p(stream if stream is not None else torch.cuda.current_stream(self.dev).cuda_stream)
-
-
 class CostResult:
     """snap_cost_batch: cost [B] f64, grad_times (layout of times, or None), status [B] i32."""
     __slots__ = ("cost", "grad_times", "status")
@@ -617,14 +549,15 @@ def snap_cost_batch(waypoints, times, bc=None, order=4, vel_zero_weight=0.0, seg
     """The cost J the solve minimises at `times` and its gradient dJ/dtimes (csp_minsnap_cost_batch).
     Inputs as in solve_batch without the path penalty: numpy arrays -> host memory, torch CUDA tensors -> device memory
     (asynchronous on the current stream)."""
-    ci = _CallInputs(waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj)
-    cost = ci.empty((ci.B,), "f64")
-    grad = ci.empty(tuple(ci.times.shape), "io") if want_grad else None
-    stt = ci.empty((ci.B,), "i32")
-    wsp, need = ci.workspace(cost_workspace_bytes(ci.desc), workspace)
-    p = ci.ptr
-    _check(_lib.csp_minsnap_cost_batch(ctypes.byref(ci.desc), p(ci.waypoints), p(ci.times), p(ci.bc), p(cost), p(grad), p(stt),
-                                       wsp, need, ci.stream(stream)))
+    ci = _CallInputs(waypoints, times, bc, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    mem, p = ci.mem, ci.mem.ptr
+    desc = ci.desc(order, ci.checked_bc_per_trajectory(), 0.0, vel_zero_weight)
+    cost = mem.empty((ci.B,), "f64")
+    grad = mem.empty(ci.times.shape, ci.io) if want_grad else None
+    stt = mem.empty((ci.B,), "i32")
+    wsp, need = mem.workspace(cost_workspace_bytes(desc), workspace)
+    _check(_lib.csp_minsnap_cost_batch(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(ci.bc), p(cost), p(grad), p(stt),
+                                       wsp, need, mem.stream(stream)))
     return CostResult(cost, grad, stt)
 
 
@@ -650,20 +583,19 @@ def optimize_times_batch(waypoints, times, bc=None, order=4, mode="fixed_total",
     Inputs as in snap_cost_batch."""
     if mode not in _TIMEOPT_MODES:
         raise ValueError("mode: one of %r" % (tuple(_TIMEOPT_MODES),))
-    ci = _CallInputs(waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    ci = _CallInputs(waypoints, times, bc, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    mem, p = ci.mem, ci.mem.ptr
+    desc = ci.desc(order, ci.checked_bc_per_trajectory(), 0.0, vel_zero_weight)
     prm = make_timeopt_params(_TIMEOPT_MODES[mode], time_weight, min_time, tol, max_iters)
-    tout = ci.empty(tuple(ci.times.shape), "io")
-    total = int(ci.times.numel() if ci.torch else ci.times.size)
-    co = ci.empty((total, 3, 2 * int(order)) if ci.seg_offsets is not None else (ci.B, ci.times.shape[1], 3, 2 * int(order)),
-                  "io") if want_coeffs else None
-    obj = ci.empty((ci.B, 2), "f64")
-    its = ci.empty((ci.B,), "i32")
-    stt = ci.empty((ci.B,), "i32")
-    wsp, need = ci.workspace(timeopt_workspace_bytes(ci.desc), workspace)
-    p = ci.ptr
-    _check(_lib.csp_minsnap_optimize_times_batch(ctypes.byref(ci.desc), ctypes.byref(prm), p(ci.waypoints), p(ci.times),
+    tout = mem.empty(ci.times.shape, ci.io)
+    co = mem.empty(ci.coeffs_shape(order), ci.io) if want_coeffs else None
+    obj = mem.empty((ci.B, 2), "f64")
+    its = mem.empty((ci.B,), "i32")
+    stt = mem.empty((ci.B,), "i32")
+    wsp, need = mem.workspace(timeopt_workspace_bytes(desc), workspace)
+    _check(_lib.csp_minsnap_optimize_times_batch(ctypes.byref(desc), ctypes.byref(prm), p(ci.waypoints), p(ci.times),
                                                  p(ci.bc), p(tout), p(co), p(obj), p(its), p(stt), wsp, need,
-                                                 ci.stream(stream)))
+                                                 mem.stream(stream)))
     return TimeOptResult(tout, co, obj, its, stt)
 
 
@@ -687,17 +619,16 @@ def solve_periodic_batch(waypoints, times, order=4, vel_zero_weight=0.0, seg_off
     closing point), times [B,S]; ragged: waypoints [sum S_b,3] and times [sum S_b], both split by seg_offsets [B+1].
     numpy arrays -> host memory, torch CUDA tensors -> device memory (asynchronous on the current stream).  want_cost /
     want_grad add the snap cost J and dJ/dtimes; the coefficients are the same bits either way."""
-    ci = _CallInputs(waypoints, times, None, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj)
-    m = 2 * int(order)
-    total = int(ci.times.numel() if ci.torch else ci.times.size)
-    co = ci.empty((total, 3, m) if ci.seg_offsets is not None else (ci.B, ci.times.shape[1], 3, m), "io")
-    cost = ci.empty((ci.B,), "f64") if want_cost else None
-    grad = ci.empty(tuple(ci.times.shape), "io") if want_grad else None
-    stt = ci.empty((ci.B,), "i32")
-    wsp, need = ci.workspace(periodic_workspace_bytes(ci.desc), workspace)
-    p = ci.ptr
-    _check(_lib.csp_minsnap_solve_periodic_batch(ctypes.byref(ci.desc), p(ci.waypoints), p(ci.times), p(co), p(cost),
-                                                 p(grad), p(stt), wsp, need, ci.stream(stream)))
+    ci = _CallInputs(waypoints, times, None, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    mem, p = ci.mem, ci.mem.ptr
+    desc = ci.desc(order, ci.checked_bc_per_trajectory(), 0.0, vel_zero_weight)
+    co = mem.empty(ci.coeffs_shape(order), ci.io)
+    cost = mem.empty((ci.B,), "f64") if want_cost else None
+    grad = mem.empty(ci.times.shape, ci.io) if want_grad else None
+    stt = mem.empty((ci.B,), "i32")
+    wsp, need = mem.workspace(periodic_workspace_bytes(desc), workspace)
+    _check(_lib.csp_minsnap_solve_periodic_batch(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(co), p(cost),
+                                                 p(grad), p(stt), wsp, need, mem.stream(stream)))
     return PeriodicResult(co, cost, grad, stt)
 
 
@@ -741,20 +672,18 @@ class PreparedMulti:
     buckets -- over n independent uniform batches of one shape (lists of CUDA tensors [B_k,S+1,3] / [B_k,S])."""
 
     def __init__(self, waypoints, times, bcs=None, order=4, vel_zero_weight=0.0, want_status=False, stream=None):
-        import torch
         n = len(waypoints)
-        self.dev, tdt = waypoints[0].device, waypoints[0].dtype
+        mem = _DeviceMem(waypoints[0])
+        self.dev, io = mem.dev, mem.kind(waypoints[0])
         S = times[0].shape[1]
-        m = 2 * int(order)
-        self.wp = [w.contiguous() for w in waypoints]
-        self.tm = [t.to(tdt).contiguous() for t in times]
-        zero = torch.zeros((1, 4, 3), dtype=tdt, device=self.dev)
-        self.bc = [zero if (bcs is None or bcs[k] is None) else bcs[k].to(tdt).contiguous().reshape(-1, 4, 3) for k in range(n)]
-        per = self.bc[0].shape[0] != 1
-        self.out = [torch.empty((t.shape[0], S, 3, m), dtype=tdt, device=self.dev) for t in self.tm]
-        self.status = [torch.empty(t.shape[0], dtype=torch.int32, device=self.dev) for t in self.tm] if want_status else None
-        self.desc = make_desc(order, 0, S, DTYPE_F32 if tdt == torch.float32 else DTYPE_F64, 0.0, vel_zero_weight, MEM_DEVICE, per,
-                              device_id=self.dev.index if self.dev.index is not None else -1)
+        self.wp = [mem.contig(w, io) for w in waypoints]
+        self.tm = [mem.contig(t, io) for t in times]
+        zero = _bc_block(mem, None, io)
+        self.bc = [zero if (bcs is None or bcs[k] is None) else _bc_block(mem, bcs[k], io) for k in range(n)]
+        self.out = [mem.empty((t.shape[0], S, 3, 2 * int(order)), io) for t in self.tm]
+        self.status = [mem.empty((t.shape[0],), "i32") for t in self.tm] if want_status else None
+        self.desc = make_desc(order, 0, S, _dtype_code(io), 0.0, vel_zero_weight, MEM_DEVICE, self.bc[0].shape[0] != 1,
+                              device_id=mem.device_id)
         arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
         self._keep = (arr(self.wp), arr(self.tm), arr(self.bc), arr(self.out), arr(self.status) if want_status else None,
                       (ctypes.c_int64 * n)(*[t.shape[0] for t in self.tm]))
@@ -802,27 +731,19 @@ class PreparedMixed:
 
     def __init__(self, orders, waypoints, times, seg_offsets, bc=None, vel_zero_weight=0.0, max_segments=None, out=None,
                  want_status=False, stream=None):
-        import torch
         if not (_is_torch(waypoints) and waypoints.is_cuda):
             raise ValueError("PreparedMixed takes CUDA tensors (device memory space)")
-        self.dev, tdt = waypoints.device, waypoints.dtype
-        dtype = DTYPE_F32 if tdt == torch.float32 else DTYPE_F64
-        self.wp, self.tm = waypoints.contiguous(), times.to(tdt).contiguous()
-        self.off = seg_offsets.to(device=self.dev, dtype=torch.int64).contiguous()
-        self.orders = orders.to(device=self.dev, dtype=torch.int32).contiguous()
-        B = self.off.numel() - 1
-        if max_segments is None:
-            max_segments = int((self.off[1:] - self.off[:-1]).max().item()) if B else 1
-        self.bc = (torch.zeros((1, 4, 3), dtype=tdt, device=self.dev) if bc is None else bc.to(tdt).contiguous().reshape(-1, 4, 3))
-        self.total = mixed_coeff_total(self.orders, self.off, dtype == DTYPE_F32)
-        self.out = out if out is not None else torch.empty(max(self.total, 1), dtype=tdt, device=self.dev)
-        self.coeff_offsets = torch.empty(B + 1, dtype=torch.int64, device=self.dev)
-        self.status = torch.empty(B, dtype=torch.int32, device=self.dev) if want_status else None
-        self.desc = make_desc(0, B, 0, dtype, 0.0, vel_zero_weight, MEM_DEVICE, self.bc.shape[0] == B and B != 1,
-                              seg_offsets_ptr=self.off.data_ptr(), max_segments=max_segments,
-                              device_id=self.dev.index if self.dev.index is not None else -1, flags=0)
+        ci = _CallInputs(waypoints, times, bc, seg_offsets, max_segments)
+        mem, B = ci.mem, ci.B
+        self.dev, self.wp, self.tm, self.off, self.bc = mem.dev, ci.waypoints, ci.times, ci.seg_offsets, ci.bc
+        self.orders = mem.contig(orders, "i32")
+        self.total = mixed_coeff_total(self.orders, self.off, ci.io == "f32")
+        self.out = out if out is not None else mem.empty(max(self.total, 1), ci.io)
+        self.coeff_offsets = mem.empty(B + 1, "i64")
+        self.status = mem.empty(B, "i32") if want_status else None
+        self.desc = ci.desc(0, ci.bc.shape[0] == B and B != 1, 0.0, vel_zero_weight)
         self.ws_bytes = _lib.csp_minsnap_mixed_workspace_bytes(ctypes.byref(self.desc))
-        self.ws = torch.empty(max(self.ws_bytes, 1), dtype=torch.uint8, device=self.dev)
+        self.ws = mem.empty(max(self.ws_bytes, 1), "u8")
         self._stream = stream
         self._args = (ctypes.byref(self.desc), self.orders.data_ptr(), self.wp.data_ptr(), self.tm.data_ptr(), self.bc.data_ptr(),
                       self.out.data_ptr(), self.coeff_offsets.data_ptr(), self.status.data_ptr() if want_status else None,
@@ -844,37 +765,25 @@ def solve_mixed(orders, waypoints, times, seg_offsets, bc=None, vel_zero_weight=
     numpy inputs -> CSP_MEM_HOST, torch CUDA tensors -> CSP_MEM_DEVICE.  Returns MixedResult.  `out` (host form only): the
     flat coefficient array to write, of at least mixed_coeff_total() elements; the blocks of skipped trajectories keep
     their contents."""
-    if _is_torch(waypoints):
-        import torch
+    if _is_torch(waypoints):   # the device form is one PreparedMixed, run once
         if vel_zero_weight_per_traj is not None or out is not None:
             raise ValueError("per-trajectory weights or a given output: use the host-memory form or PreparedMixed")
         p = PreparedMixed(orders, waypoints, times, seg_offsets, bc, vel_zero_weight, max_segments, want_status=want_status, stream=stream)
         p.run()
         return MixedResult(p.out, p.coeff_offsets, p.status)
-    waypoints = np.asarray(waypoints)
-    dtype = DTYPE_F32 if waypoints.dtype == np.float32 else DTYPE_F64
-    npdt = _np_dtype(dtype)
-    waypoints = np.ascontiguousarray(waypoints, dtype=npdt)
-    times = np.ascontiguousarray(times, dtype=npdt)
-    seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.int64)
-    orders = np.ascontiguousarray(orders, dtype=np.int32)
-    B = seg_offsets.shape[0] - 1
-    if max_segments is None:
-        max_segments = int(np.max(np.diff(seg_offsets))) if B else 1
-    bc = np.zeros((1, 4, 3), dtype=npdt) if bc is None else np.ascontiguousarray(bc, dtype=npdt).reshape(-1, 4, 3)
-    need = max(mixed_coeff_total(orders, seg_offsets, dtype == DTYPE_F32), 1)
+    ci = _CallInputs(waypoints, times, bc, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    mem, p, B = ci.mem, ci.mem.ptr, ci.B
+    orders = mem.contig(orders, "i32")
+    need = max(mixed_coeff_total(orders, ci.seg_offsets, ci.io == "f32"), 1)
     if out is None:
-        out = np.empty(need, dtype=npdt)
-    elif not (isinstance(out, np.ndarray) and out.dtype == npdt and out.flags.c_contiguous and out.size >= need):
-        raise ValueError("out: a contiguous %s array of at least %d elements" % (np.dtype(npdt).name, need))
-    cof = np.empty(B + 1, dtype=np.int64)
-    stt = np.empty(B, dtype=np.int32) if want_status else None
-    vwp = np.ascontiguousarray(vel_zero_weight_per_traj, dtype=np.float64) if vel_zero_weight_per_traj is not None else None
-    desc = make_desc(0, B, 0, dtype, 0.0, vel_zero_weight, MEM_HOST, bc.shape[0] == B and B != 1, seg_offsets.ctypes.data, max_segments,
-                     vwp.ctypes.data if vwp is not None else None, -1, 0)
-    rc = _lib.csp_minsnap_solve_mixed(ctypes.byref(desc), orders.ctypes.data, waypoints.ctypes.data, times.ctypes.data, bc.ctypes.data,
-                                      out.ctypes.data, cof.ctypes.data, stt.ctypes.data if stt is not None else None, None, 0, None)
-    _check(rc)
+        out = mem.empty(need, ci.io)
+    elif not (isinstance(out, np.ndarray) and out.dtype == _DTYPE_NAME[ci.io] and out.flags.c_contiguous and out.size >= need):
+        raise ValueError("out: a contiguous %s array of at least %d elements" % (_DTYPE_NAME[ci.io], need))
+    cof = mem.empty(B + 1, "i64")
+    stt = mem.empty(B, "i32") if want_status else None
+    desc = ci.desc(0, ci.bc.shape[0] == B and B != 1, 0.0, vel_zero_weight)
+    _check(_lib.csp_minsnap_solve_mixed(ctypes.byref(desc), p(orders), p(ci.waypoints), p(ci.times), p(ci.bc), p(out), p(cof),
+                                        p(stt), None, 0, None))
     return MixedResult(out, cof, stt)
 
 
@@ -886,35 +795,21 @@ class PreparedSolve:
     def __init__(self, waypoints, times, bc=None, order=4, path_weight=0.0, vel_zero_weight=0.0, out=None,
                  force_generic=False, segment_major=False, no_persistent=False, stream=None,
                  seg_offsets=None, max_segments=None, span=False):
-        import torch
         if not (_is_torch(waypoints) and waypoints.is_cuda):
             raise ValueError("PreparedSolve takes CUDA tensors (device memory space)")
-        self.dev, tdt = waypoints.device, waypoints.dtype
-        dtype = DTYPE_F32 if tdt == torch.float32 else DTYPE_F64
-        self.wp, self.tm = waypoints.contiguous(), times.to(tdt).contiguous()
         ragged = seg_offsets is not None
-        m = 2 * int(order)
+        if ragged and segment_major:
+            raise ValueError("segment_major needs a uniform batch")
+        ci = _CallInputs(waypoints, times, bc, seg_offsets, max_segments if ragged else None)
+        mem, B = ci.mem, ci.B
+        self.dev, self.wp, self.tm, self.bc = mem.dev, ci.waypoints, ci.times, ci.bc
         if ragged:   # concatenated trajectories: waypoints [sum(S_b)+B,3], times [sum S_b], offsets [B+1] on the device
-            if segment_major:
-                raise ValueError("segment_major needs a uniform batch")
-            self.off = seg_offsets.to(device=self.dev, dtype=torch.int64).contiguous()
-            B, S = self.off.numel() - 1, 0
-            total = self.tm.numel()
-            if max_segments is None:
-                max_segments = int((self.off[1:] - self.off[:-1]).max().item()) if B else 1
-        else:
-            B, S = self.tm.shape
-        self.bc = (torch.zeros((1, 4, 3), dtype=tdt, device=self.dev) if bc is None
-                   else bc.to(tdt).contiguous().reshape(-1, 4, 3))
-        shape = (total, 3, m) if ragged else ((S, B, 3, m) if segment_major else (B, S, 3, m))
-        self.out = out if out is not None else torch.empty(shape, dtype=tdt, device=self.dev)
-        flags = ((FLAG_FORCE_GENERIC if force_generic else 0) | (FLAG_SEGMENT_MAJOR if segment_major else 0)
-                 | (FLAG_NO_PERSISTENT if no_persistent else 0) | (FLAG_SPAN if span else 0))
-        self.desc = make_desc(order, B, S, dtype, path_weight, vel_zero_weight, MEM_DEVICE, self.bc.shape[0] == B and B != 1,
-                              seg_offsets_ptr=self.off.data_ptr() if ragged else None, max_segments=(max_segments or 0) if ragged else 0,
-                              device_id=self.dev.index if self.dev.index is not None else -1, flags=flags)
+            self.off = ci.seg_offsets
+        self.out = out if out is not None else mem.empty(ci.coeffs_shape(order, segment_major), ci.io)
+        self.desc = ci.desc(order, ci.bc.shape[0] == B and B != 1, path_weight, vel_zero_weight,
+                            _flags(force_generic, segment_major, no_persistent, span=span))
         self.ws_bytes = workspace_bytes(self.desc)
-        self.ws = torch.empty(max(self.ws_bytes, 1), dtype=torch.uint8, device=self.dev)
+        self.ws = mem.empty(max(self.ws_bytes, 1), "u8")
         self.kernel = kernel_name(self.desc)
         self._stream = stream
         self._args = (ctypes.byref(self.desc), self.wp.data_ptr(), self.tm.data_ptr(), self.bc.data_ptr(),
@@ -932,43 +827,21 @@ class PreparedSolve:
 
 def time_alloc_batch(waypoints, v_avg, min_time_s, seg_offsets=None, stream=None):
     """Batched T_i = max(|dp_i|/V_avg, min_time_s) (math_util/minimum_snap.cpp:63-72)."""
-    ragged = seg_offsets is not None
-    if _is_torch(waypoints):
-        import torch
-        dev, tdt = waypoints.device, waypoints.dtype
-        dtype = DTYPE_F32 if tdt == torch.float32 else DTYPE_F64
-        waypoints = waypoints.contiguous()
-        if ragged:
-            seg_offsets = seg_offsets.to(device=dev, dtype=torch.int64).contiguous()
-            B = seg_offsets.numel() - 1
-            times = torch.empty(waypoints.shape[0] - B, dtype=tdt, device=dev)
-            S = 0
-        else:
-            B, S = waypoints.shape[0], waypoints.shape[1] - 1
-            times = torch.empty((B, S), dtype=tdt, device=dev)
-        desc = make_desc(1, B, S, dtype, mem_space=MEM_DEVICE,
-                         seg_offsets_ptr=seg_offsets.data_ptr() if ragged else None, max_segments=1 if ragged else 0,
-                         device_id=dev.index if dev.index is not None else -1)
-        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-        _check(_lib.csp_minsnap_time_alloc_batch(ctypes.byref(desc), waypoints.data_ptr(), float(v_avg),
-                                                 float(min_time_s), times.data_ptr(), ctypes.c_void_p(st)))
-        return times
-    waypoints = np.asarray(waypoints)
-    dtype = DTYPE_F32 if waypoints.dtype == np.float32 else DTYPE_F64
-    npdt = _np_dtype(dtype)
-    waypoints = np.ascontiguousarray(waypoints, dtype=npdt)
-    if ragged:
-        seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.int64)
-        B = seg_offsets.shape[0] - 1
-        times = np.empty(waypoints.shape[0] - B, dtype=npdt)
-        S = 0
+    mem = _mem(waypoints)
+    io = mem.kind(waypoints)
+    waypoints = mem.contig(waypoints, io)
+    off = None
+    if seg_offsets is not None:
+        off = mem.contig(seg_offsets, "i64")
+        B, S = off.shape[0] - 1, 0
+        times = mem.empty(waypoints.shape[0] - B, io)
     else:
         B, S = waypoints.shape[0], waypoints.shape[1] - 1
-        times = np.empty((B, S), dtype=npdt)
-    desc = make_desc(1, B, S, dtype, mem_space=MEM_HOST,
-                     seg_offsets_ptr=seg_offsets.ctypes.data if ragged else None, max_segments=1 if ragged else 0)
-    _check(_lib.csp_minsnap_time_alloc_batch(ctypes.byref(desc), waypoints.ctypes.data, float(v_avg),
-                                             float(min_time_s), times.ctypes.data, None))
+        times = mem.empty((B, S), io)
+    desc = make_desc(1, B, S, _dtype_code(io), mem_space=mem.mem_space, seg_offsets_ptr=mem.ptr(off),
+                     max_segments=1 if off is not None else 0, device_id=mem.device_id)
+    _check(_lib.csp_minsnap_time_alloc_batch(ctypes.byref(desc), mem.ptr(waypoints), float(v_avg), float(min_time_s),
+                                             mem.ptr(times), mem.stream(stream)))
     return times
 
 
@@ -976,62 +849,50 @@ class Plan:
     __slots__ = ("times", "coeffs", "max_dev", "vel_zero_weight", "iterations", "status")
 
 
+def _plan_inputs(waypoints, bc, order, path_weight, vel_zero_weight, flags=0):
+    """(backend, storage kind, waypoints, bc, descriptor) of plan_batch / generate_batch: uniform waypoints [B,S+1,3]."""
+    mem = _mem(waypoints)
+    io = mem.kind(waypoints)
+    waypoints = mem.contig(waypoints, io)
+    B = waypoints.shape[0]
+    bc = _bc_block(mem, bc, io)
+    desc = make_desc(order, B, waypoints.shape[1] - 1, _dtype_code(io), path_weight, vel_zero_weight, mem.mem_space,
+                     bc.shape[0] == B and B != 1, device_id=mem.device_id, flags=flags)
+    return mem, io, waypoints, bc, desc
+
+
+def _plan_outputs(r, mem, io, desc):
+    """Allocates the Plan fields of `r`; returns their pointers in the C-ABI's order."""
+    B, S = desc.batch, desc.num_segments
+    r.times = mem.empty((B, S), io)
+    r.coeffs = mem.empty((B, S, 3, 2 * desc.order), io)
+    r.max_dev, r.vel_zero_weight = mem.empty(B, "f64"), mem.empty(B, "f64")
+    r.iterations, r.status = mem.empty(B, "i32"), mem.empty(B, "i32")
+    return [mem.ptr(a) for a in (r.times, r.coeffs, r.max_dev, r.vel_zero_weight, r.iterations, r.status)]
+
+
+def _plan_workspace_bytes(desc):
+    return int(_lib.csp_minsnap_plan_workspace_bytes(ctypes.byref(desc)))
+
+
 def plan_batch(waypoints, v_avg, min_time_s, bc=None, order=3, path_weight=0.0, vel_zero_weight=0.0):
     """Batched solver half of GenerateTrajectoryMatrix (math_util/minimum_snap.cpp:59-90): time
     allocation + the <=10x vel_zero_weight doubling loop.  Uniform batches, numpy (host) or torch
     CUDA tensors.  waypoints [B,S+1,3]."""
-    on_device = _is_torch(waypoints)
-    m = 2 * int(order)
+    mem, io, waypoints, bc, desc = _plan_inputs(waypoints, bc, order, path_weight, vel_zero_weight)
     r = Plan()
-    if on_device:
-        import torch
-        dev, tdt = waypoints.device, waypoints.dtype
-        dtype = DTYPE_F32 if tdt == torch.float32 else DTYPE_F64
-        waypoints = waypoints.contiguous()
-        B, S = waypoints.shape[0], waypoints.shape[1] - 1
-        bc = torch.zeros((1, 4, 3), dtype=tdt, device=dev) if bc is None else bc.to(tdt).contiguous().reshape(-1, 4, 3)
-        r.times = torch.empty((B, S), dtype=tdt, device=dev)
-        r.coeffs = torch.empty((B, S, 3, m), dtype=tdt, device=dev)
-        r.max_dev = torch.empty(B, dtype=torch.float64, device=dev)
-        r.vel_zero_weight = torch.empty(B, dtype=torch.float64, device=dev)
-        r.iterations = torch.empty(B, dtype=torch.int32, device=dev)
-        r.status = torch.empty(B, dtype=torch.int32, device=dev)
-        desc = make_desc(order, B, S, dtype, path_weight, vel_zero_weight, MEM_DEVICE, bc.shape[0] == B and B != 1,
-                         device_id=dev.index if dev.index is not None else -1)
-        need = int(_lib.csp_minsnap_plan_workspace_bytes(ctypes.byref(desc)))
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _check(_lib.csp_minsnap_plan_batch(ctypes.byref(desc), waypoints.data_ptr(), float(v_avg), float(min_time_s),
-                                           bc.data_ptr(), r.times.data_ptr(), r.coeffs.data_ptr(), r.max_dev.data_ptr(),
-                                           r.vel_zero_weight.data_ptr(), r.iterations.data_ptr(), r.status.data_ptr(),
-                                           ws.data_ptr(), need, ctypes.c_void_p(st)))
-        return r
-    waypoints = np.asarray(waypoints)
-    dtype = DTYPE_F32 if waypoints.dtype == np.float32 else DTYPE_F64
-    npdt = _np_dtype(dtype)
-    waypoints = np.ascontiguousarray(waypoints, dtype=npdt)
-    B, S = waypoints.shape[0], waypoints.shape[1] - 1
-    bc = np.zeros((1, 4, 3), dtype=npdt) if bc is None else np.ascontiguousarray(bc, dtype=npdt).reshape(-1, 4, 3)
-    r.times = np.empty((B, S), dtype=npdt)
-    r.coeffs = np.empty((B, S, 3, m), dtype=npdt)
-    r.max_dev = np.empty(B, dtype=np.float64)
-    r.vel_zero_weight = np.empty(B, dtype=np.float64)
-    r.iterations = np.empty(B, dtype=np.int32)
-    r.status = np.empty(B, dtype=np.int32)
-    desc = make_desc(order, B, S, dtype, path_weight, vel_zero_weight, MEM_HOST, bc.shape[0] == B and B != 1)
-    _check(_lib.csp_minsnap_plan_batch(ctypes.byref(desc), waypoints.ctypes.data, float(v_avg), float(min_time_s),
-                                       bc.ctypes.data, r.times.ctypes.data, r.coeffs.ctypes.data, r.max_dev.ctypes.data,
-                                       r.vel_zero_weight.ctypes.data, r.iterations.ctypes.data, r.status.ctypes.data,
-                                       None, 0, None))
+    outs = _plan_outputs(r, mem, io, desc)
+    wsp, need = _scratch(mem, _plan_workspace_bytes, desc)
+    _check(_lib.csp_minsnap_plan_batch(ctypes.byref(desc), mem.ptr(waypoints), float(v_avg), float(min_time_s), mem.ptr(bc),
+                                       *outs, wsp, need, mem.stream()))
     return r
 
 
 def sample_capacity(waypoints, v_avg, min_time_s, order=3):
     """Upper bound of the samples per trajectory (csp_minsnap_sample_capacity), from host waypoints [B,S+1,3]."""
-    waypoints = np.asarray(waypoints)
-    dtype = DTYPE_F32 if waypoints.dtype == np.float32 else DTYPE_F64
-    waypoints = np.ascontiguousarray(waypoints, dtype=_np_dtype(dtype))
-    desc = make_desc(order, waypoints.shape[0], waypoints.shape[1] - 1, dtype, mem_space=MEM_HOST)
+    io = _HOST.kind(waypoints)
+    waypoints = _HOST.contig(waypoints, io)
+    desc = make_desc(order, waypoints.shape[0], waypoints.shape[1] - 1, _dtype_code(io), mem_space=MEM_HOST)
     cap = int(_lib.csp_minsnap_sample_capacity(ctypes.byref(desc), waypoints.ctypes.data, float(v_avg), float(min_time_s)))
     if cap < 0:
         raise CspError(-1, "csp_minsnap_sample_capacity")
@@ -1043,67 +904,27 @@ class Generated(Plan):
     __slots__ = ("samples", "counts", "stats")
 
 
+def _sample_outputs(mem, io, B, capacity):
+    return mem.zeros((B, capacity, 3), io), mem.empty(B, "i32"), mem.empty((B, 2), "f64")
+
+
 def generate_batch(waypoints, v_avg, min_time_s, sample_distance, capacity=None, bc=None, order=3, path_weight=0.0,
                    vel_zero_weight=0.0, long_segments=False):
     """The whole of GenerateTrajectoryMatrix (math_util/minimum_snap.cpp:22-206) in one call
     (csp_minsnap_generate_batch = plan_batch + sample_batch, bit for bit).  Uniform batches, numpy (host: one upload,
     one download, one synchronisation) or torch CUDA tensors (asynchronous; `capacity` required)."""
-    on_device = _is_torch(waypoints)
-    m = 2 * int(order)
-    r = Generated()
-    flags = FLAG_LONG_SEGMENTS if long_segments else 0
-    if on_device:
-        import torch
-        if capacity is None:
-            raise ValueError("device-memory generate_batch needs a capacity")
-        dev, tdt = waypoints.device, waypoints.dtype
-        dtype = DTYPE_F32 if tdt == torch.float32 else DTYPE_F64
-        waypoints = waypoints.contiguous()
-        B, S = waypoints.shape[0], waypoints.shape[1] - 1
-        bc = torch.zeros((1, 4, 3), dtype=tdt, device=dev) if bc is None else bc.to(tdt).contiguous().reshape(-1, 4, 3)
-        r.times = torch.empty((B, S), dtype=tdt, device=dev)
-        r.coeffs = torch.empty((B, S, 3, m), dtype=tdt, device=dev)
-        r.max_dev = torch.empty(B, dtype=torch.float64, device=dev)
-        r.vel_zero_weight = torch.empty(B, dtype=torch.float64, device=dev)
-        r.iterations = torch.empty(B, dtype=torch.int32, device=dev)
-        r.status = torch.empty(B, dtype=torch.int32, device=dev)
-        r.samples = torch.zeros((B, capacity, 3), dtype=tdt, device=dev)
-        r.counts = torch.empty(B, dtype=torch.int32, device=dev)
-        r.stats = torch.empty((B, 2), dtype=torch.float64, device=dev)
-        desc = make_desc(order, B, S, dtype, path_weight, vel_zero_weight, MEM_DEVICE, bc.shape[0] == B and B != 1,
-                         device_id=dev.index if dev.index is not None else -1, flags=flags)
-        need = int(_lib.csp_minsnap_plan_workspace_bytes(ctypes.byref(desc)))
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _check(_lib.csp_minsnap_generate_batch(ctypes.byref(desc), waypoints.data_ptr(), float(v_avg), float(min_time_s), bc.data_ptr(),
-                                               float(sample_distance), int(capacity), r.samples.data_ptr(), r.counts.data_ptr(),
-                                               r.stats.data_ptr(), r.times.data_ptr(), r.coeffs.data_ptr(), r.max_dev.data_ptr(),
-                                               r.vel_zero_weight.data_ptr(), r.iterations.data_ptr(), r.status.data_ptr(),
-                                               ws.data_ptr(), need, ctypes.c_void_p(st)))
-        return r
-    waypoints = np.asarray(waypoints)
-    dtype = DTYPE_F32 if waypoints.dtype == np.float32 else DTYPE_F64
-    npdt = _np_dtype(dtype)
-    waypoints = np.ascontiguousarray(waypoints, dtype=npdt)
-    B, S = waypoints.shape[0], waypoints.shape[1] - 1
-    bc = np.zeros((1, 4, 3), dtype=npdt) if bc is None else np.ascontiguousarray(bc, dtype=npdt).reshape(-1, 4, 3)
-    desc = make_desc(order, B, S, dtype, path_weight, vel_zero_weight, MEM_HOST, bc.shape[0] == B and B != 1, flags=flags)
+    mem, io, waypoints, bc, desc = _plan_inputs(waypoints, bc, order, path_weight, vel_zero_weight, _flags(long_segments=long_segments))
     if capacity is None:
-        capacity = int(_lib.csp_minsnap_sample_capacity(ctypes.byref(desc), waypoints.ctypes.data, float(v_avg), float(min_time_s)))
-    r.times = np.empty((B, S), dtype=npdt)
-    r.coeffs = np.empty((B, S, 3, m), dtype=npdt)
-    r.max_dev = np.empty(B, dtype=np.float64)
-    r.vel_zero_weight = np.empty(B, dtype=np.float64)
-    r.iterations = np.empty(B, dtype=np.int32)
-    r.status = np.empty(B, dtype=np.int32)
-    r.samples = np.zeros((B, capacity, 3), dtype=npdt)
-    r.counts = np.empty(B, dtype=np.int32)
-    r.stats = np.empty((B, 2), dtype=np.float64)
-    _check(_lib.csp_minsnap_generate_batch(ctypes.byref(desc), waypoints.ctypes.data, float(v_avg), float(min_time_s), bc.ctypes.data,
-                                           float(sample_distance), int(capacity), r.samples.ctypes.data, r.counts.ctypes.data,
-                                           r.stats.ctypes.data, r.times.ctypes.data, r.coeffs.ctypes.data, r.max_dev.ctypes.data,
-                                           r.vel_zero_weight.ctypes.data, r.iterations.ctypes.data, r.status.ctypes.data,
-                                           None, 0, None))
+        if mem.mem_space == MEM_DEVICE:   # csp_minsnap_sample_capacity reads the waypoints on the host
+            raise ValueError("device-memory generate_batch needs a capacity")
+        capacity = int(_lib.csp_minsnap_sample_capacity(ctypes.byref(desc), mem.ptr(waypoints), float(v_avg), float(min_time_s)))
+    r = Generated()
+    outs = _plan_outputs(r, mem, io, desc)
+    r.samples, r.counts, r.stats = _sample_outputs(mem, io, desc.batch, capacity)
+    wsp, need = _scratch(mem, _plan_workspace_bytes, desc)
+    _check(_lib.csp_minsnap_generate_batch(ctypes.byref(desc), mem.ptr(waypoints), float(v_avg), float(min_time_s), mem.ptr(bc),
+                                           float(sample_distance), int(capacity), mem.ptr(r.samples), mem.ptr(r.counts),
+                                           mem.ptr(r.stats), *outs, wsp, need, mem.stream()))
     return r
 
 
@@ -1116,63 +937,30 @@ def sample_batch(times, coeffs, sample_distance, capacity, order=None, out=None,
     `long_segments` (device path) selects the wave-per-trajectory kernel for legs of hundreds of candidates
     (the host path decides from the times).  Ragged batches (host arrays): times [sum S_b], coeffs [sum S_b,3,2o],
     `seg_offsets` [B+1]."""
-    on_device = _is_torch(times)
-    if seg_offsets is not None:
-        if on_device:
-            raise ValueError("ragged sampling takes host arrays here")
-        seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.int64)
-        B, S = seg_offsets.shape[0] - 1, 0
-    else:
-        B, S = times.shape
+    mem = _mem(times)
+    device = mem.mem_space == MEM_DEVICE
+    if seg_offsets is not None and device:
+        raise ValueError("ragged sampling takes host arrays here")
+    io = mem.kind(times)
+    times, coeffs = mem.contig(times, io), mem.contig(coeffs, io)
+    off, B, S, _, smax = _ragged_dims(mem, seg_offsets, times, None)
     order = int(order) if order is not None else int(coeffs.shape[-1]) // 2
-    if on_device:
-        import torch
-        dev, tdt = times.device, times.dtype
-        dtype = DTYPE_F32 if tdt == torch.float32 else DTYPE_F64
-        times, coeffs = times.contiguous(), coeffs.to(tdt).contiguous()
-        if out is not None:
-            samples, counts, stats = out
-        else:
-            samples = torch.zeros((B, capacity, 3), dtype=tdt, device=dev)
-            counts = torch.empty(B, dtype=torch.int32, device=dev)
-            stats = torch.empty((B, 2), dtype=torch.float64, device=dev)
-        desc = make_desc(order, B, S, dtype, mem_space=MEM_DEVICE, device_id=dev.index if dev.index is not None else -1,
-                         flags=(FLAG_FORCE_GENERIC if one_lane else 0) | (FLAG_LONG_SEGMENTS if long_segments else 0))
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _check(_lib.csp_minsnap_sample_batch(ctypes.byref(desc), times.data_ptr(), coeffs.data_ptr(), float(sample_distance),
-                                             int(capacity), samples.data_ptr(), counts.data_ptr(), stats.data_ptr(),
-                                             ctypes.c_void_p(st)))
-        return samples, counts, stats
-    times = np.asarray(times)
-    dtype = DTYPE_F32 if times.dtype == np.float32 else DTYPE_F64
-    npdt = _np_dtype(dtype)
-    times = np.ascontiguousarray(times, dtype=npdt)
-    coeffs = np.ascontiguousarray(coeffs, dtype=npdt)
-    samples = np.zeros((B, capacity, 3), dtype=npdt)
-    counts = np.empty(B, dtype=np.int32)
-    stats = np.empty((B, 2), dtype=np.float64)
-    desc = make_desc(order, B, S, dtype, mem_space=MEM_HOST,
-                     seg_offsets_ptr=seg_offsets.ctypes.data if seg_offsets is not None else None,
-                     max_segments=int(np.max(np.diff(seg_offsets))) if seg_offsets is not None and B else 0,
-                     flags=(FLAG_FORCE_GENERIC if one_lane else 0) | (FLAG_LONG_SEGMENTS if long_segments else 0))
-    _check(_lib.csp_minsnap_sample_batch(ctypes.byref(desc), times.ctypes.data, coeffs.ctypes.data, float(sample_distance),
-                                         int(capacity), samples.ctypes.data, counts.ctypes.data, stats.ctypes.data, None))
+    # a host-memory call always returns fresh arrays: `out` is the device path's
+    samples, counts, stats = out if out is not None and device else _sample_outputs(mem, io, B, capacity)
+    desc = make_desc(order, B, S, _dtype_code(io), mem_space=mem.mem_space, seg_offsets_ptr=mem.ptr(off),
+                     max_segments=smax if off is not None and B else 0, device_id=mem.device_id,
+                     flags=_flags(force_generic=one_lane, long_segments=long_segments))
+    _check(_lib.csp_minsnap_sample_batch(ctypes.byref(desc), mem.ptr(times), mem.ptr(coeffs), float(sample_distance),
+                                         int(capacity), mem.ptr(samples), mem.ptr(counts), mem.ptr(stats), mem.stream()))
     return samples, counts, stats
 
 
 def _geo(fn, pts, ref):
     ref = np.ascontiguousarray(ref, dtype=np.float64).reshape(3)
-    if _is_torch(pts):
-        import torch
-        pts = pts.to(torch.float64).contiguous()
-        out = torch.empty_like(pts)
-        st = torch.cuda.current_stream(pts.device).cuda_stream
-        _check(fn(pts.data_ptr(), ref.ctypes.data, out.data_ptr(), pts.shape[0], MEM_DEVICE,
-                  pts.device.index if pts.device.index is not None else -1, ctypes.c_void_p(st)))
-        return out
-    pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
-    out = np.empty_like(pts)
-    _check(fn(pts.ctypes.data, ref.ctypes.data, out.ctypes.data, pts.shape[0], MEM_HOST, -1, None))
+    mem = _mem(pts)
+    pts = mem.contig(pts, "f64").reshape(-1, 3)
+    out = mem.empty(pts.shape, "f64")
+    _check(fn(mem.ptr(pts), ref.ctypes.data, mem.ptr(out), pts.shape[0], mem.mem_space, mem.device_id, mem.stream()))
     return out
 
 
@@ -1187,32 +975,18 @@ def enu_to_wgs84_batch(enu, ref):
     return _geo(_lib.csp_geo_enu_to_wgs84_batch, enu, ref)
 
 
-class AltParams(ctypes.Structure):
-    """Mirror of `csp_alt_params` (include/csp_alt.h; reference AltitudeParams, uavPathPlanning.hpp:415-421)."""
-    _fields_ = [("lambda_smooth", ctypes.c_double), ("lambda_follow", ctypes.c_double),
-                ("safe_distance", ctypes.c_double), ("max_climb_rate", ctypes.c_double)]
-
-
-_lib.csp_alt_workspace_bytes.restype = ctypes.c_size_t
-_lib.csp_alt_workspace_bytes.argtypes = [ctypes.c_int64]
-_lib.csp_alt_optimize_heights_batch.restype = ctypes.c_int
-_lib.csp_alt_optimize_heights_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                ctypes.POINTER(AltParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                                ctypes.c_uint32, ctypes.c_int32, ctypes.c_void_p]
-_lib.csp_alt_global_smooth_batch.restype = ctypes.c_int
-_lib.csp_alt_global_smooth_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                             ctypes.POINTER(AltParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int32, ctypes.c_void_p]
-
-
 def _alt_params(lambda_smooth, lambda_follow, safe_distance, max_climb_rate):
     return AltParams(float(lambda_smooth), float(lambda_follow), float(safe_distance), float(max_climb_rate))
 
 
 def _alt_ws_bytes(total):
-    _lib.csp_alt_workspace_bytes.restype = ctypes.c_size_t
-    _lib.csp_alt_workspace_bytes.argtypes = [ctypes.c_int64]
     return int(_lib.csp_alt_workspace_bytes(int(total)))
+
+
+def _alt_inputs(xyz, z, offsets):
+    """(backend, xyz [total,3], elev or input_z [total], offsets [B+1]) of the altitude entries, all fp64."""
+    mem = _mem(xyz)
+    return mem, mem.contig(xyz, "f64").reshape(-1, 3), mem.contig(z, "f64"), mem.contig(offsets, "i64")
 
 
 def alt_optimize_heights_batch(xyz, elev, offsets, lambda_smooth=1.0, lambda_follow=0.0, safe_distance=50.0,
@@ -1220,26 +994,13 @@ def alt_optimize_heights_batch(xyz, elev, offsets, lambda_smooth=1.0, lambda_fol
     """Batched UavPathPlanner::optimizeHeights (uavPathPlanning.cpp:1575-1713).  numpy arrays (host memory) or torch CUDA
     tensors (device memory): xyz [total,3], elev [total] (NaN = no terrain sample), offsets [B+1].  Returns z [total]."""
     p = _alt_params(lambda_smooth, lambda_follow, safe_distance, max_climb_rate)
-    if _is_torch(xyz):
-        import torch
-        dev = xyz.device
-        xyz = xyz.to(torch.float64).contiguous().reshape(-1, 3)
-        elev = elev.to(torch.float64).contiguous()
-        offsets = offsets.to(device=dev, dtype=torch.int64).contiguous()
-        out = torch.empty(xyz.shape[0], dtype=torch.float64, device=dev)
-        need = _alt_ws_bytes(xyz.shape[0])
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        _check(_lib.csp_alt_optimize_heights_batch(xyz.data_ptr(), elev.data_ptr(), offsets.data_ptr(), offsets.numel() - 1, ctypes.byref(p),
-                                                   out.data_ptr(), ws.data_ptr(), need, MEM_DEVICE, dev.index if dev.index is not None else -1,
-                                                   ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        torch.cuda.current_stream(dev).synchronize()   # `ws` must outlive the kernel
-        return out
-    xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-    elev = np.ascontiguousarray(elev, dtype=np.float64)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    out = np.empty(xyz.shape[0])
-    _check(_lib.csp_alt_optimize_heights_batch(xyz.ctypes.data, elev.ctypes.data, offsets.ctypes.data, offsets.shape[0] - 1,
-                                               ctypes.byref(p), out.ctypes.data, None, 0, MEM_HOST, -1, None))
+    mem, xyz, elev, offsets = _alt_inputs(xyz, elev, offsets)
+    a, total = mem.addr, xyz.shape[0]
+    out = mem.empty(total, "f64")
+    wsp, need = _scratch(mem, _alt_ws_bytes, total)
+    _check(_lib.csp_alt_optimize_heights_batch(a(xyz), a(elev), a(offsets), offsets.shape[0] - 1, ctypes.byref(p), a(out),
+                                               wsp, need, mem.mem_space, mem.device_id, mem.stream()))
+    mem.sync()   # the workspace is a local: it must outlive the kernel
     return out
 
 
@@ -1247,60 +1008,25 @@ def alt_global_smooth_batch(input_z, xyz, offsets, lambda_smooth=1.0, max_climb_
     """Batched UavPathPlanner::optimizeHeightsGlobalSmooth (uavPathPlanning.cpp:1715-1827).
     Returns (z [total], solves [B]); numpy (host memory) or torch CUDA tensors (device memory)."""
     p = _alt_params(lambda_smooth, 0.0, 0.0, max_climb_rate)
-    if _is_torch(xyz):
-        import torch
-        dev = xyz.device
-        xyz = xyz.to(torch.float64).contiguous().reshape(-1, 3)
-        input_z = input_z.to(torch.float64).contiguous()
-        offsets = offsets.to(device=dev, dtype=torch.int64).contiguous()
-        out = torch.empty(xyz.shape[0], dtype=torch.float64, device=dev)
-        solves = torch.empty(offsets.numel() - 1, dtype=torch.int32, device=dev)
-        need = _alt_ws_bytes(xyz.shape[0])
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        _check(_lib.csp_alt_global_smooth_batch(input_z.data_ptr(), xyz.data_ptr(), offsets.data_ptr(), offsets.numel() - 1, ctypes.byref(p),
-                                                out.data_ptr(), solves.data_ptr(), ws.data_ptr(), need, MEM_DEVICE,
-                                                dev.index if dev.index is not None else -1,
-                                                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        torch.cuda.current_stream(dev).synchronize()
-        return out, solves
-    xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-    input_z = np.ascontiguousarray(input_z, dtype=np.float64)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    out = np.empty(xyz.shape[0])
-    solves = np.empty(offsets.shape[0] - 1, dtype=np.int32)
-    _check(_lib.csp_alt_global_smooth_batch(input_z.ctypes.data, xyz.ctypes.data, offsets.ctypes.data, offsets.shape[0] - 1,
-                                            ctypes.byref(p), out.ctypes.data, solves.ctypes.data, None, 0, MEM_HOST, -1, None))
+    mem, xyz, input_z, offsets = _alt_inputs(xyz, input_z, offsets)
+    a, total, B = mem.addr, xyz.shape[0], offsets.shape[0] - 1
+    out, solves = mem.empty(total, "f64"), mem.empty(B, "i32")
+    wsp, need = _scratch(mem, _alt_ws_bytes, total)
+    _check(_lib.csp_alt_global_smooth_batch(a(input_z), a(xyz), a(offsets), B, ctypes.byref(p), a(out), a(solves), wsp, need,
+                                            mem.mem_space, mem.device_id, mem.stream()))
+    mem.sync()   # as above
     return out, solves
-
-
-_lib.csp_bezier_generate_batch.restype = ctypes.c_int
-_lib.csp_bezier_generate_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_double,
-                                           ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32,
-                                           ctypes.c_void_p]
 
 
 def bezier_generate_batch(waypoints, offsets, resolution=1.0, min_radius=1.0, capacity=4096):
     """Batched math_util::Bezier::GenerateTrajectoryMatrix (math_util/bezier.cpp:127-190; include/csp_bezier.h).
     waypoints [total,3] (paths concatenated), offsets [B+1] point prefix sums; numpy (host) or torch CUDA tensors.
     Returns (samples [B,capacity,3], counts [B])."""
-    if _is_torch(waypoints):
-        import torch
-        dev = waypoints.device
-        wp = waypoints.to(torch.float64).contiguous()
-        off = offsets.to(device=dev, dtype=torch.int64).contiguous()
-        B = off.numel() - 1
-        samples = torch.zeros((B, capacity, 3), dtype=torch.float64, device=dev)
-        counts = torch.empty(B, dtype=torch.int32, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _check(_lib.csp_bezier_generate_batch(wp.data_ptr(), off.data_ptr(), B, float(resolution), float(min_radius), int(capacity),
-                                              samples.data_ptr(), counts.data_ptr(), MEM_DEVICE,
-                                              dev.index if dev.index is not None else -1, ctypes.c_void_p(st)))
-        return samples, counts
-    wp = np.ascontiguousarray(waypoints, dtype=np.float64).reshape(-1, 3)
-    off = np.ascontiguousarray(offsets, dtype=np.int64)
+    mem = _mem(waypoints)
+    wp = mem.contig(waypoints, "f64").reshape(-1, 3)
+    off = mem.contig(offsets, "i64")
     B = off.shape[0] - 1
-    samples = np.zeros((B, capacity, 3))
-    counts = np.empty(B, dtype=np.int32)
-    _check(_lib.csp_bezier_generate_batch(wp.ctypes.data, off.ctypes.data, B, float(resolution), float(min_radius), int(capacity),
-                                          samples.ctypes.data, counts.ctypes.data, MEM_HOST, -1, None))
+    samples, counts = mem.zeros((B, capacity, 3), "f64"), mem.empty(B, "i32")
+    _check(_lib.csp_bezier_generate_batch(mem.ptr(wp), mem.ptr(off), B, float(resolution), float(min_radius), int(capacity),
+                                          mem.ptr(samples), mem.ptr(counts), mem.mem_space, mem.device_id, mem.stream()))
     return samples, counts
