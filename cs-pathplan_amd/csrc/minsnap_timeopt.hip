@@ -286,13 +286,16 @@ __global__ void __launch_bounds__(64) minsnap_timeopt_kernel(TimeOptArgs a) {
             C += t;
             feasible = feasible && t >= lo;
         }
-        if (!(C == C) || C > 1.7976931348623157e308) status |= CSP_TRAJ_NONFINITE_BIT;
-        if (ft && status == 0 && C < double(S) * lo) {
-            // device memory: the C-ABI could not check the total on the host.  Left as it came, reported not converged.
+        // an inf / NaN time: the total has no projection (Michelot's theta would be NaN and every entry would come
+        // back as min_time), and there is no start to evaluate
+        const bool nonfinite = !(fabs(C) <= 1.7976931348623157e308);
+        if (nonfinite || (ft && C < double(S) * lo)) {
+            // an infeasible fixed total -- device memory: the C-ABI could not check it on the host -- is reported not
+            // converged.  Either way the times are left as they came and nothing was evaluated.
             for (int j = 0; j < S; ++j) tout[j] = tin[j];
             if (a.objective) { a.objective[2 * b] = __builtin_nan(""); a.objective[2 * b + 1] = __builtin_nan(""); }
             if (a.iterations) a.iterations[b] = 0;
-            if (a.status) a.status[b] = CSP_TRAJ_NOT_CONVERGED_BIT;
+            if (a.status) a.status[b] = nonfinite ? CSP_TRAJ_NONFINITE_BIT : CSP_TRAJ_NOT_CONVERGED_BIT;
             return;
         }
         const double th0 = feasible ? 0.0 : proj_theta([&](int j) { return double(tin[j]); }, S, ft, C, lo);

@@ -205,13 +205,18 @@ typedef struct csp_minsnap_timeopt_params {
  *                 min_time <= 0, tol < 0, max_iters < 0, and (CSP_MEM_HOST) sum_j T_j^in < S * min_time with the fixed
  *                 total.  With CSP_MEM_DEVICE the last check is per trajectory on the device: such a trajectory is
  *                 returned unchanged with CSP_TRAJ_NOT_CONVERGED, iterations 0 and NaN objectives.
+ *   times_in    : an entry below min_time (zero and negative ones included) is not an error: the start is the
+ *                 projection.  A trajectory with an inf / NaN time has no projection and is returned unchanged with
+ *                 CSP_TRAJ_NONFINITE, iterations 0 and NaN objectives.  S = 1 with the fixed total has nothing to
+ *                 optimise: times_out = times_in bit for bit, final objective = initial objective, iterations 0.
  *   times_out   : out, the layout of times_in
  *   coeffs      : optional out, csp_minsnap_solve_batch(times_out) -- computed by that call's own dispatch, so bit-equal
  *                 to a separate solve
  *   objective   : optional out, [B][2] f64: initial (at the start) and final objective (J, plus rho sum T)
  *   iterations  : optional out, [B] i32 accepted iterations
- *   status      : optional out, [B] i32: CSP_TRAJ_NOT_SPD / CSP_TRAJ_NONFINITE (the trajectory stops at its last
- *                 accepted times), CSP_TRAJ_NOT_CONVERGED
+ *   status      : optional out, [B] i32: CSP_TRAJ_NOT_SPD / CSP_TRAJ_NONFINITE (the solve failed at the start, e.g. an
+ *                 inf / NaN waypoint or bc: the trajectory stops there, times_out = the start, iterations 0),
+ *                 CSP_TRAJ_NOT_CONVERGED.  A bad trajectory does not change any output of another one.
  *   workspace   : device scratch of csp_minsnap_timeopt_workspace_bytes(desc) bytes (CSP_MEM_DEVICE, 8-byte aligned);
  *                 may be NULL/0 with CSP_MEM_HOST:
  *                   round_up_256((Smax - 1) * ((o-1)^2 + 3(o-1)) * B * 8) + 4 * Smax * B * 8

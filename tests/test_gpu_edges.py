@@ -19,6 +19,7 @@ import pytest
 
 import oracle
 from tests import synth
+from tests.staged import STAGED as _STAGED, staged_buffers as _staged_buffers
 
 pytestmark = pytest.mark.gpu
 
@@ -321,43 +322,6 @@ def test_mixed_entry_over_long_trajectories_in_both_forms(csp, oracle_mod):
             # the dense oracle's gates of tests/test_gpu_round3.py (measured here: 2.4e-10 per power)
             _gates(blk[:6 * o * n].reshape(n, 3, 2 * o), ref, 1e-6 if o == 5 else 5e-8, ("mixed skip", i, o, n))
     assert np.array_equal(h.coeffs, out_d)
-
-
-# The five entries that stage host memory the same way: C symbol, workspace function, and per pointer argument
-# (name, "in" / "out", required).  Shapes and element types are in _staged_buffers.
-_STAGED = {
-    "solve_batch": ("csp_minsnap_solve_batch", "csp_minsnap_workspace_bytes",
-                    (("waypoints", "in", True), ("times", "in", True), ("bc", "in", True), ("coeffs", "out", True),
-                     ("max_dev", "out", False), ("status", "out", False))),
-    "solve_batch_vjp": ("csp_minsnap_solve_batch_vjp", "csp_minsnap_vjp_workspace_bytes",
-                        (("waypoints", "in", True), ("times", "in", True), ("bc", "in", True), ("grad_coeffs", "in", True),
-                         ("grad_waypoints", "out", False), ("grad_times", "out", False), ("grad_bc", "out", False),
-                         ("status", "out", False))),
-    "cost_batch": ("csp_minsnap_cost_batch", "csp_minsnap_cost_workspace_bytes",
-                   (("waypoints", "in", True), ("times", "in", True), ("bc", "in", True), ("cost", "out", True),
-                    ("grad_times", "out", False), ("status", "out", False))),
-    "optimize_times_batch": ("csp_minsnap_optimize_times_batch", "csp_minsnap_timeopt_workspace_bytes",
-                             (("waypoints", "in", True), ("times", "in", True), ("bc", "in", True), ("times_out", "out", True),
-                              ("coeffs", "out", False), ("objective", "out", False), ("iterations", "out", False),
-                              ("status", "out", False))),
-    "solve_periodic_batch": ("csp_minsnap_solve_periodic_batch", "csp_minsnap_periodic_workspace_bytes",
-                             (("waypoints", "in", True), ("times", "in", True), ("coeffs", "out", True), ("cost", "out", False),
-                              ("grad_times", "out", False), ("status", "out", False))),
-}
-
-
-def _staged_buffers(entry, lens, order, f32, bc_per, seed):
-    """Host arrays of every pointer argument of `entry` for trajectories of `lens` segments (outputs zeroed)."""
-    rng = np.random.default_rng(seed)
-    io = np.float32 if f32 else np.float64
-    B, total, m = len(lens), int(np.sum(lens)), 2 * order
-    n_wp = total if entry == "solve_periodic_batch" else total + B   # a closed loop has no repeated end point
-    b = dict(waypoints=np.cumsum(rng.normal(size=(n_wp, 3)), axis=0).astype(io), times=rng.uniform(0.5, 2.0, size=total).astype(io),
-             bc=rng.normal(size=(B if bc_per else 1, 4, 3)).astype(io), grad_coeffs=rng.normal(size=(total, 3, m)).astype(io))
-    b.update(coeffs=np.zeros((total, 3, m), io), grad_waypoints=np.zeros((n_wp, 3), io), grad_times=np.zeros(total, io),
-             grad_bc=np.zeros_like(b["bc"]), times_out=np.zeros(total, io), max_dev=np.zeros(B), cost=np.zeros(B),
-             objective=np.zeros((B, 2)), status=np.zeros(B, np.int32), iterations=np.zeros(B, np.int32))
-    return b
 
 
 @pytest.mark.parametrize("entry", sorted(_STAGED))
