@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcsp_minsnap.so")
 # The per-order kernel files dominate the build (1-3 CPU-minutes each, most expensive first); the parallel build starts
 # them before everything else.
-HEAVY = ["minsnap_fixed_o4b.hip", "minsnap_fixed_o4c.hip", "minsnap_fixed_o4a.hip",
+HEAVY = ["minsnap_fixed_o4b.hip", "minsnap_fixed_o4c.hip", "minsnap_fixed_o4a.hip", "minsnap_fixed_o4d.hip",
          "minsnap_fixedpath_o4b.hip", "minsnap_fixedpath_o4c.hip", "minsnap_fixedpath_o4a.hip",
          "minsnap_fixedpath_o3b.hip", "minsnap_fixedpath_o3.hip", "minsnap_fixedpath_o2.hip",
          "minsnap_fixed_o3.hip", "minsnap_fixed_o2.hip", "minsnap_fixed_o5.hip"]

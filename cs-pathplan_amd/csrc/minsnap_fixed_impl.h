@@ -57,6 +57,9 @@ namespace fixedk {
 // The flavour is a template parameter: as a run-time select every store was a pair of branches around both flavours,
 // which cut the bursts into two-instruction basic blocks.
 typedef double v2d_t __attribute__((ext_vector_type(2)));
+// Store policy of a full-slice kernel's coefficient stores, a compile-time property of the instantiation: ordinary,
+// non-temporal, or (values >= 16) write-through with that value as the buffer store's cache bits.
+constexpr int SP_PLAIN = 0, SP_NT = 1, SP_WT = 16;
 template <bool NT> __device__ __forceinline__ void store16(char *p, const double2 &v) {
     if constexpr (NT) {
         v2d_t x = {v.x, v.y};
@@ -75,16 +78,33 @@ __device__ __forceinline__ unsigned burst_off(unsigned voff) {
 // store16 at (wave-uniform base) + (32-bit lane byte offset from burst_off), for the unpredicated bursts: the shape the
 // scalar-base form of the global store expresses (base in an SGPR pair, offset in one VGPR), so a burst carries no
 // per-store 64-bit vector address arithmetic.  `ubase` MUST be wave-uniform: it is pinned in scalar registers.
-template <bool NT> __device__ __forceinline__ void store16u(char *ubase, unsigned voff, const double2 &v) {
+// SP: the store policy (below).  A write-through policy keeps ORDINARY stores here: this form also carries the single
+// records, whose lines are shared between two store instructions and have to meet in L2.
+template <int SP> __device__ __forceinline__ void store16u(char *ubase, unsigned voff, const double2 &v) {
     typedef __attribute__((address_space(1))) v2d_t *gptr_t;
     // The empty statement pins the base (displacement included) in a scalar register pair: left to itself hipcc
     // re-associates the sum to (base + lane offset) + displacement and carries a 64-bit vector address per store.
     unsigned long long u = reinterpret_cast<unsigned long long>(ubase);
+#ifdef CSP_STAMPS
+    // diagnostic build only: around the stamp stores hipcc carries the slice base in vector registers, which the scalar
+    // pin below cannot take ("illegal VGPR to SGPR copy")
+    // (the builtin returns int: without the casts the low half would be sign-extended over the high one)
+    u = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(u >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((unsigned)u);
+#endif
     asm("" : "+s"(u));
     gptr_t p = reinterpret_cast<gptr_t>(u + voff);
     const v2d_t x = {v.x, v.y};
-    if constexpr (NT) __builtin_nontemporal_store(x, p);
+    if constexpr (SP == SP_NT) __builtin_nontemporal_store(x, p);
     else *p = x;
+}
+// 16-byte WRITE-THROUGH store at descriptor base + wave-uniform displacement + 32-bit lane offset:
+// buffer_store_dwordx4 with the cache bits of AUX (16 = sc1, 17 = sc0 sc1).  The line goes to memory and is dropped from
+// the XCD's L2 instead of staying there dirty until the write-back that ends the kernel.  Only for bursts in which every
+// store instruction writes whole 128-byte lines (the paired order-4 records): write-through stores are not merged.
+typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
+template <int AUX> __device__ __forceinline__ void store16wt(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned disp, const double2 &v) {
+    const v2d_t x = {v.x, v.y};
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_t, x), rsrc, (int)voff, (int)disp, AUX);
 }
 
 __device__ __forceinline__ void lds_barrier() {
@@ -260,7 +280,7 @@ template <int O, int S, bool BOTTOM> struct LineRing {
                 for (int i = 0; i < 8; ++i)
                     if (pv && (!PRED || ((live8 >> i) & 1u))) {
                         if constexpr (PRED) store16<NT>(tbase + ell * 128 + (size_t)i * 8 * RS + g_lane, v[i]);
-                        else store16u<NT>(tbase + ell * 128 + (size_t)i * 8 * RS, g_lane, v[i]);
+                        else store16u<NT ? SP_NT : SP_PLAIN>(tbase + ell * 128 + (size_t)i * 8 * RS, g_lane, v[i]);
                     }
             }
         }
@@ -342,12 +362,12 @@ template <bool BOTTOM> struct RoleBc {
 // NAX = 3: one lane per trajectory (all three axes).  NAX = 1 (small batches, see launch_s): THREE lanes per trajectory,
 // lane = (axis ax0, staging row `row`), each factorising redundantly and carrying one right-hand side -- about half the
 // instructions per lane, which is what a lone latency-bound wave is made of.
-template <int O, int S, bool BOTTOM, bool STATUS, bool FULL, bool SEGMAJ, bool STASH, bool NT, class In, class Hook, int NAX = 3>
+template <int O, int S, bool BOTTOM, bool STATUS, bool FULL, bool SEGMAJ, bool STASH, int SP, class In, class Hook, int NAX = 3>
 __device__ __forceinline__ void fixed_body(const GenericArgs &a, int64_t b0, int64_t b, int lane,
                                            const In &in, const RoleBc<BOTTOM> &rbc, double *stage, double *partner_stage,
                                            double *tst, const Hook &after_exchange, int rows = 64, int row_ = 0, int ax0 = 0) {
     static_assert(NAX == 3 || (NAX == 1 && !FULL && !STASH), "the axis-per-lane mapping serves the narrow one-slice kernel only");
-    static_assert(FULL || !NT, "only the full-slice kernels have a non-temporal flavour");
+    static_assert(FULL || SP == SP_PLAIN, "only the full-slice kernels have a store policy");
     const int row = NAX == 3 ? lane : row_;   // staging-tile row = trajectory within the slice
     constexpr int N = O - 1, M = 2 * O;
     constexpr int HS = BOTTOM ? S / 2 : (S + 1) / 2;   // segments of THIS role; both roles meet at waypoint ceil(S/2)
@@ -493,6 +513,8 @@ __device__ __forceinline__ void fixed_body(const GenericArgs &a, int64_t b0, int
     // 256-byte run.  Every line is then written whole (the single-record scheme left 1/3 of the lines
     // half-written between two bursts and measured +8 % WRITE_SIZE).  Lane maps of the burst shapes:
     constexpr bool PAIRING = FULL && !SEGMAJ && O == 4 && (S % 2) == 0;
+    constexpr bool WT = SP >= SP_WT;
+    static_assert(!WT || PAIRING, "write-through stores need the paired whole-line bursts");
     // the other orders: whole-line ring (LineRing above) wherever the trajectories start on 128-byte lines
     constexpr bool RING = FULL && !SEGMAJ && !PAIRING && NAX == 3 && LineGeom<O, S>::OK;
     using LR = LineRing<O, S, BOTTOM>;
@@ -582,14 +604,38 @@ __device__ __forceinline__ void fixed_body(const GenericArgs &a, int64_t b0, int
         if (paired) {
             // pair base = record of the even segment; TOP meets the odd record first, BOTTOM the even one
             char *pbase = reinterpret_cast<char *>((double *)a.coeffs + (b0 * S + (g & ~1)) * L::REC);  // uniform
-            if (first) {
+            if constexpr (WT) {
+                // the same bursts through a descriptor of the slice's 64 * S records: lane offset in the vector operand,
+                // pair and row displacement in the scalar one
+                const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+                    reinterpret_cast<char *>((double *)a.coeffs + b0 * S * L::REC), 0, 64 * RS, 0x00020000);
+                const unsigned pdisp = (unsigned)((g & ~1) * RECB);
+                if (first) {
+                    double2 v[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const double2 *>(stage + l8 + i * 8 * ROW);
+#pragma unroll
+                    for (int i = 0; i < 8; ++i)
+                        store16wt<SP>(rsrc, o8, pdisp + (BOTTOM ? 0 : 256) + (unsigned)(i * 8 * RS), v[i]);
+                } else {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        double2 v[8];
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const double2 *>(stage + l16 + (h * 8 + i) * 4 * ROW);
+#pragma unroll
+                        for (int i = 0; i < 8; ++i)
+                            store16wt<SP>(rsrc, o16, pdisp + (BOTTOM ? 128 : 0) + (unsigned)((h * 8 + i) * 4 * RS), v[i]);
+                    }
+                }
+            } else if (first) {
                 const unsigned o8b = burst_off(o8);
                 double2 v[8];   // 8 rows x 128 bytes per store
 #pragma unroll
                 for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const double2 *>(stage + l8 + i * 8 * ROW);
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
-                    store16u<NT>(pbase + (BOTTOM ? 0 : 256) + (size_t)i * 8 * RS, o8b, v[i]);
+                    store16u<SP>(pbase + (BOTTOM ? 0 : 256) + (size_t)i * 8 * RS, o8b, v[i]);
             } else {
                 const unsigned o16b = burst_off(o16);
 #pragma unroll
@@ -599,11 +645,11 @@ __device__ __forceinline__ void fixed_body(const GenericArgs &a, int64_t b0, int
                     for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const double2 *>(stage + l16 + (h * 8 + i) * 4 * ROW);
 #pragma unroll
                     for (int i = 0; i < 8; ++i)
-                        store16u<NT>(pbase + (BOTTOM ? 128 : 0) + (size_t)(h * 8 + i) * 4 * RS, o16b, v[i]);
+                        store16u<SP>(pbase + (BOTTOM ? 128 : 0) + (size_t)(h * 8 + i) * 4 * RS, o16b, v[i]);
                 }
             }
         } else if (RING) {
-            LR::template flush<false, NT>(g, stage, reinterpret_cast<char *>((double *)a.coeffs + b0 * S * L::REC), lane, 0xffu);
+            LR::template flush<false, SP == SP_NT>(g, stage, reinterpret_cast<char *>((double *)a.coeffs + b0 * S * L::REC), lane, 0xffu);
         } else {
             char *gbase = reinterpret_cast<char *>((double *)a.coeffs + (SEGMAJ ? ((int64_t)g * a.Btotal + a.Boffset + b0) : (b0 * S + g)) * L::REC);  // uniform
             if (FULL) {
@@ -617,9 +663,9 @@ __device__ __forceinline__ void fixed_body(const GenericArgs &a, int64_t b0, int
                     for (int i = 0; i < NFULL; ++i)
                         v[i] = *reinterpret_cast<const double2 *>(stage + lds_off + i * L::RPI * ROW);
 #pragma unroll
-                    for (int i = 0; i < NFULL; ++i) store16u<NT>(gbase + (size_t)i * L::RPI * RS, g_offb, v[i]);
+                    for (int i = 0; i < NFULL; ++i) store16u<SP>(gbase + (size_t)i * L::RPI * RS, g_offb, v[i]);
                     if (NFULL < L::NI && NFULL * L::RPI + grp < 64)   // the ragged last store
-                        store16u<NT>(gbase + (size_t)NFULL * L::RPI * RS, g_offb,
+                        store16u<SP>(gbase + (size_t)NFULL * L::RPI * RS, g_offb,
                                      *reinterpret_cast<const double2 *>(stage + lds_off + NFULL * L::RPI * ROW));
                 }
             } else {
@@ -743,13 +789,13 @@ __global__ void __launch_bounds__(128) minsnap_fixed_kernel(GenericArgs a, Multi
         const LdsInputs<S, false> in{l_wp, l_tm, row};
         RoleBc<false> rbc;
         rbc.load(a, b);
-        fixed_body<O, S, false, STATUS, FULL, SEGMAJ, false, NT, LdsInputs<S, false>, NoHook, NAX>(
+        fixed_body<O, S, false, STATUS, FULL, SEGMAJ, false, NT ? SP_NT : SP_PLAIN, LdsInputs<S, false>, NoHook, NAX>(
             a, b0, b, lane, in, rbc, l_stage, l_stage + L::STAGE_DOUBLES, nullptr, NoHook{}, rows, row, ax0);
     } else {
         const LdsInputs<S, true> in{l_wp, l_tm, row};
         RoleBc<true> rbc;
         rbc.load(a, b);
-        fixed_body<O, S, true, STATUS, FULL, SEGMAJ, false, NT, LdsInputs<S, true>, NoHook, NAX>(
+        fixed_body<O, S, true, STATUS, FULL, SEGMAJ, false, NT ? SP_NT : SP_PLAIN, LdsInputs<S, true>, NoHook, NAX>(
             a, b0, b, lane, in, rbc, l_stage + L::STAGE_DOUBLES, l_stage, nullptr, NoHook{}, rows, row, ax0);
     }
 }
@@ -797,7 +843,7 @@ template <int S> struct SlicePrefetch {
     __device__ __forceinline__ void operator()() const { if (next < n_slices) issue(next); }
 };
 
-template <int O, int S, bool BOTTOM, bool STATUS, bool SEGMAJ, bool NT>
+template <int O, int S, bool BOTTOM, bool STATUS, bool SEGMAJ, int SP>
 __device__ __forceinline__ void persistent_role_loop(const GenericArgs &a, int n_slices, int lane, const double *l_wp,
                                                      const double *l_tm, double *stage, double *partner_stage,
                                                      double *tst, SlicePrefetch<S> pf) {
@@ -806,7 +852,8 @@ __device__ __forceinline__ void persistent_role_loop(const GenericArgs &a, int n
     // Vector-memory operations a wave issues AFTER a slice's prefetch and before the next top-of-loop
     // wait: its store bursts.  Must not be over-estimated (the counted wait below relies on at least
     // this many younger operations existing).  Paired records (order 4, default layout): 8 + 16
-    // stores per pair; single records: NI each.
+    // stores per pair; single records: NI each.  The write-through bursts are buffer stores, one vector-memory
+    // operation each like the global stores they replace.
     constexpr int PAIRS = (SEGMAJ || O != 4 || (S % 2) != 0) ? 0 : HS / 2;
     constexpr bool RING = !SEGMAJ && O != 4 && LineGeom<O, S>::OK;   // as in fixed_body: 8 stores per line of the role
     constexpr int STORES_PER_SLICE = RING ? LineRing<O, S, BOTTOM>::LINES * 8 : PAIRS * 24 + (HS - 2 * PAIRS) * L::NI;
@@ -828,7 +875,7 @@ __device__ __forceinline__ void persistent_role_loop(const GenericArgs &a, int n
         const int64_t b0 = slice * 64;
         pf.next = slice + gridDim.x;
         // the image is dead once both waves passed the exchange barrier: prefetch the next slice there
-        fixed_body<O, S, BOTTOM, STATUS, true, SEGMAJ, true, NT>(a, b0, b0 + lane, lane, in, rbc, stage, partner_stage, tst, pf);
+        fixed_body<O, S, BOTTOM, STATUS, true, SEGMAJ, true, SP>(a, b0, b0 + lane, lane, in, rbc, stage, partner_stage, tst, pf);
         first = false;
     }
 }
@@ -836,8 +883,8 @@ __device__ __forceinline__ void persistent_role_loop(const GenericArgs &a, int n
 // Persistent variant for the full workgroups of a batch: gridDim.x workgroups (two per CU) walk the
 // batch with stride gridDim.x; the NEXT slice's inputs stream into LDS while the current slice is
 // back-substituted and stored, so only a workgroup's very first copy-in is exposed.
-template <int O, int S, bool STATUS, bool SEGMAJ, bool NT>
-__global__ void __launch_bounds__(128) minsnap_fixed_persistent_kernel(GenericArgs a, int n_slices) {
+template <int O, int S, bool STATUS, bool SEGMAJ, int SP>
+__device__ __forceinline__ void persistent_kernel_body(const GenericArgs &a, int n_slices) {
     using L = FixedLds<O, S>;
     // image (waypoints, times) | two staging tiles | two time stashes (the forward sweep parks the
     // segment times it read there: the image is overwritten by the prefetch during the backward sweep)
@@ -861,9 +908,23 @@ __global__ void __launch_bounds__(128) minsnap_fixed_persistent_kernel(GenericAr
     CSP_STAMP(0);
     if ((int64_t)blockIdx.x < n_slices) pf.issue(blockIdx.x);
     // one loop per role: each wave's instruction stream holds a single specialisation
-    if (role == 0) persistent_role_loop<O, S, false, STATUS, SEGMAJ, NT>(a, n_slices, lane, l_wp, l_tm, l_stage, l_stage + L::STAGE_DOUBLES, l_tst, pf);
-    else persistent_role_loop<O, S, true, STATUS, SEGMAJ, NT>(a, n_slices, lane, l_wp, l_tm, l_stage + L::STAGE_DOUBLES, l_stage, l_tst + L::HT * 64, pf);
+    if (role == 0) persistent_role_loop<O, S, false, STATUS, SEGMAJ, SP>(a, n_slices, lane, l_wp, l_tm, l_stage, l_stage + L::STAGE_DOUBLES, l_tst, pf);
+    else persistent_role_loop<O, S, true, STATUS, SEGMAJ, SP>(a, n_slices, lane, l_wp, l_tm, l_stage + L::STAGE_DOUBLES, l_stage, l_tst + L::HT * 64, pf);
 }
+
+template <int O, int S, bool STATUS, bool SEGMAJ, bool NT>
+__global__ void __launch_bounds__(128) minsnap_fixed_persistent_kernel(GenericArgs a, int n_slices) {
+    persistent_kernel_body<O, S, STATUS, SEGMAJ, NT ? SP_NT : SP_PLAIN>(a, n_slices);
+}
+// The same kernel with write-through stores in its paired bursts (AUX: the buffer store's cache bits, SP_WT = sc1): default
+// layout, order 4, even S only -- every other shape stores partial lines per instruction, which write-through would send
+// to the fabric unmerged.  Instantiated in minsnap_fixed_o4d.hip alone.
+template <int O, int S, bool STATUS, int AUX>
+__global__ void __launch_bounds__(128) minsnap_fixed_persistent_wt_kernel(GenericArgs a, int n_slices) {
+    static_assert(O == 4 && S % 2 == 0 && AUX >= SP_WT, "write-through covers the paired order-4 records");
+    persistent_kernel_body<O, S, STATUS, false, AUX>(a, n_slices);
+}
+hipError_t launch_persistent_wt_o4(const GenericArgs &f, int n_slices, unsigned grid, hipStream_t st);   // minsnap_fixed_o4d.hip
 
 // ---- host side: launch one order's kernels -----------------------------------------------------
 // Trajectories per workgroup for the one-workgroup-per-slice kernel.  A small batch is latency-bound -- a lone wave's
@@ -892,6 +953,31 @@ inline int nt_stores_for(int64_t B, int S, int O) {
     const int forced = nt_forced();
     if (forced >= 0) return forced;
     return (double)B * S * 6 * O * 8.0 > 256.0 * 1024 * 1024 ? 1 : 0;
+}
+
+// Store policy of a launch's whole slices (SP_PLAIN / SP_NT / SP_WT), from the bytes of coefficients it writes.
+// Write-through exists for the paired order-4 records only (wt_shape: even S >= 4; default layout, persistent kernel), and
+// launch_s asks this rule for those shapes alone: every other shape keeps nt_stores_for.  CSP_STORE_POLICY=plain|nt|wt
+// forces the choice for them (A/B runs) and takes precedence over CSP_NT_STORES; a forced `wt` that meets the
+// one-workgroup-per-slice kernel (CSP_FLAG_NO_PERSISTENT, per-trajectory boundary conditions) stores ordinarily.  Up to the
+// chip's aggregate L2 (8 x 4 MiB) the stores stay ordinary whatever the sweep says: a following kernel
+// (the sampler after a plan) still finds those lines in L2.  Above the Infinity Cache: non-temporal, as before.
+constexpr double WT_ABOVE_BYTES = 32.0 * 1024 * 1024, WT_UP_TO_BYTES = 256.0 * 1024 * 1024;
+inline int store_policy_forced() {
+    static const int forced = [] {
+        const char *e = std::getenv("CSP_STORE_POLICY");
+        if (!e) return -1;
+        return e[0] == 'w' ? SP_WT : (e[0] == 'n' ? SP_NT : SP_PLAIN);
+    }();
+    return forced;
+}
+constexpr bool wt_shape(int S, int O) { return O == 4 && S >= 4 && S % 2 == 0; }
+inline int store_policy_for(double bytes, int S, int O) {
+    const int forced = store_policy_forced();
+    if (forced >= 0) return forced;
+    if (nt_forced() >= 0) return nt_forced() ? SP_NT : SP_PLAIN;
+    if (bytes > WT_ABOVE_BYTES && bytes <= WT_UP_TO_BYTES && wt_shape(S, O)) return SP_WT;
+    return bytes > WT_UP_TO_BYTES ? SP_NT : SP_PLAIN;
 }
 
 template <int O, int S, bool SEGMAJ_OK>
@@ -953,13 +1039,20 @@ hipError_t launch_s(const GenericArgs &a, int cus, hipStream_t st) {
             // ones (round 2, B = 524288: 261 / 392 / 312 us ordinary against 499 / 841 / 404 us non-temporal).
             constexpr bool WHOLE_LINES = !SM && (O == 4 || LineGeom<O, S>::OK);
             f.nt_stores = (WHOLE_LINES || O == 4) ? nt_stores_for(a.B, S, O) : (nt_forced() == 1 ? 1 : 0);
+            bool wt = false;
+            if constexpr (wt_shape(S, O) && !SM) {
+                const int sp = store_policy_for((double)a.B * S * 6 * O * 8.0, S, O);
+                wt = sp == SP_WT && a.persistent && !a.bc_per_traj && !a.vw_per;
+                if (store_policy_forced() >= 0) f.nt_stores = sp == SP_NT;
+            }
             // the store flavour is a compile-time property of the kernel: one instantiation each
             auto full = [&](auto nt_tag) {
                 constexpr bool NT = decltype(nt_tag)::value;
                 if (a.persistent && !a.bc_per_traj && !a.vw_per) hipLaunchKernelGGL((minsnap_fixed_persistent_kernel<O, S, ST, SM, NT>), dim3((unsigned)pgrid), block, 0, st, f, (int)n_full);
                 else hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, ST, true, SM, 3, NT>), dim3((unsigned)n_full), block, 0, st, f, MultiTable{});
             };
-            if (f.nt_stores) full(std::true_type{});
+            if (wt) (void)launch_persistent_wt_o4(f, (int)n_full, (unsigned)pgrid, st);
+            else if (f.nt_stores) full(std::true_type{});
             else full(std::false_type{});
         }
         if (rem) hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, ST, false, SM>), dim3(1), block, 0, st, t, MultiTable{});

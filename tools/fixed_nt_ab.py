@@ -1,6 +1,7 @@
 """A/B of non-temporal coefficient stores in the unpenalised register-resident kernels, per order:
     CSP_NT_STORES=0 python tools/fixed_nt_ab.py [orders] [B:S,B:S,...] ; CSP_NT_STORES=1 python tools/fixed_nt_ab.py ...
-(no CSP_NT_STORES: the launcher's own rule).  Default orders 2,3,4,5 at B = 524288 / 262144 x S = 16 and B = 524288 x S = 8."""
+(no CSP_NT_STORES: the launcher's own rule).  CSP_STORE_POLICY=plain|nt|wt does the same for the three-way store policy of
+the order-4 persistent kernel.  Default orders 2,3,4,5 at B = 524288 / 262144 x S = 16 and B = 524288 x S = 8."""
 import importlib
 import json
 import os
@@ -20,7 +21,7 @@ for o in orders:
         if o == 5 and S > 8:
             continue
         rec, prep, wp, tm = bench.bench_uniform(csp, dev, B, S, o, 20, 3, 3)
-        print(json.dumps({"nt_env": os.environ.get("CSP_NT_STORES"), "order": o, "B": B, "S": S, "kernel": rec["kernel"],
+        print(json.dumps({"nt_env": os.environ.get("CSP_NT_STORES"), "policy_env": os.environ.get("CSP_STORE_POLICY"), "order": o, "B": B, "S": S, "kernel": rec["kernel"],
                           "us": round(rec["kernel_ms"] * 1e3, 1), "frac_hbm": round(rec["frac_of_hbm_peak"], 3)}), flush=True)
         del prep
         torch.cuda.empty_cache()
