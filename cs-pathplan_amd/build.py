@@ -24,6 +24,9 @@ HEADERS = ["minsnap_device.h", "minsnap_launch.h", "minsnap_hoststage.h", "minsn
            os.path.join("..", "..", "include", "csp_minsnap.h"), os.path.join("..", "..", "include", "csp_geo.h"), os.path.join("..", "..", "include", "csp_alt.h"), os.path.join("..", "..", "include", "csp_bezier.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
+# Time allocation is the header's formula with every operation rounded on its own, as the reference's CPU code evaluates
+# it: -ffp-contract=fast fuses whatever a source-level pragma says, so the file is compiled without contraction.
+FILE_FLAGS = {"minsnap_timealloc.hip": ["-ffp-contract=off"]}
 OBJDIR = os.path.join(HERE, "build")
 
 
@@ -46,7 +49,7 @@ def _compile_all(extra, tag, verbose):
         if os.path.exists(obj) and all(os.path.getmtime(d) <= os.path.getmtime(obj) for d in deps):
             jobs.append((None, obj))
         else:
-            jobs.append(([HIPCC] + FLAGS + extra + ["-c", srcp, "-o", obj], obj))
+            jobs.append(([HIPCC] + FLAGS + FILE_FLAGS.get(src, []) + extra + ["-c", srcp, "-o", obj], obj))
 
     def run(job):
         cmd, obj = job

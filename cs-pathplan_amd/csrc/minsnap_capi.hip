@@ -1269,7 +1269,8 @@ int csp_minsnap_sample_batch(const csp_minsnap_desc *desc, const void *times, co
 namespace {
 
 // Host-side estimate of the segment times (minimum_snap.cpp:59-72) for SIZING only: the device computes them again
-// (possibly an ulp away: fused multiply-adds), so every count derived from these carries slack.
+// (in the storage type: with fp32 storage an ulp of fp32 away from this fp64 estimate), so every count derived from these
+// carries slack.
 void estimate_times(const csp_minsnap_desc *desc, const Shape &s, const void *waypoints, double v_avg, double min_time_s,
                     std::vector<double> &T) {
     const int64_t total_seg = s.ragged ? desc->seg_offsets[s.B] : s.B * (int64_t)s.S;

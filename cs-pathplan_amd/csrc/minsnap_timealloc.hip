@@ -5,6 +5,20 @@
 
 namespace csp {
 
+// T = max(|p1 - p0| / V_avg, min_time_s) of the segment whose start point is p[0..2], every operation rounded on its
+// own in the storage type: the header's formula as the reference's CPU code evaluates it (minimum_snap.cpp:63-72), bit
+// for bit.  Contracted into fused multiply-adds the length is an ulp off on one segment in fourteen
+// (tests/test_gpu_bounds_fast.py::test_time_alloc), so build.py compiles this file with -ffp-contract=off (under the
+// library's -ffp-contract=fast the backend fuses whatever a pragma here says).
+template <typename R>
+__device__ __forceinline__ R segment_time(const TimeAllocArgs &a, const R *p) {
+    const R dx = p[3] - p[0], dy = p[4] - p[1], dz = p[5] - p[2];
+    const R len = sqrt(dx * dx + dy * dy + dz * dz);
+    R t = (a.v_avg > 1e-6) ? (R)(len / (R)a.v_avg) : (R)a.min_time_s;
+    if (t < (R)a.min_time_s) t = (R)a.min_time_s;
+    return t;
+}
+
 template <typename R>
 __global__ void __launch_bounds__(256) time_alloc_kernel(TimeAllocArgs a, int64_t total_seg) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -21,12 +35,7 @@ __global__ void __launch_bounds__(256) time_alloc_kernel(TimeAllocArgs a, int64_
     } else {
         b = g / a.S;
     }
-    const R *p = (const R *)a.wp + (g + b) * 3;
-    const R dx = p[3] - p[0], dy = p[4] - p[1], dz = p[5] - p[2];
-    const R len = sqrt(dx * dx + dy * dy + dz * dz);
-    R t = (a.v_avg > 1e-6) ? (R)(len / (R)a.v_avg) : (R)a.min_time_s;
-    if (t < (R)a.min_time_s) t = (R)a.min_time_s;
-    ((R *)a.times)[g] = t;
+    ((R *)a.times)[g] = segment_time<R>(a, (const R *)a.wp + (g + b) * 3);
 }
 
 // Uniform batches: lane g < B*S allocates segment g's time, lane g < B initialises trajectory g's loop state.
@@ -38,12 +47,7 @@ __global__ void __launch_bounds__(256) time_alloc_init_kernel(TimeAllocArgs a, i
     if (g < a.B) { if (vw) vw[g] = vw0; iters[g] = 0; done[g] = 0; }   // vw null: the caller copies per-trajectory weights in
     if (g >= total_seg) return;
     const int64_t b = g / a.S;
-    const R *p = (const R *)a.wp + (g + b) * 3;
-    const R dx = p[3] - p[0], dy = p[4] - p[1], dz = p[5] - p[2];
-    const R len = sqrt(dx * dx + dy * dy + dz * dz);
-    R t = (a.v_avg > 1e-6) ? (R)(len / (R)a.v_avg) : (R)a.min_time_s;
-    if (t < (R)a.min_time_s) t = (R)a.min_time_s;
-    ((R *)a.times)[g] = t;
+    ((R *)a.times)[g] = segment_time<R>(a, (const R *)a.wp + (g + b) * 3);
 }
 
 hipError_t launch_time_alloc_init(const TimeAllocArgs &a, bool f32, double *vw, int32_t *iters, int32_t *done, int32_t *pending,

@@ -331,7 +331,8 @@ size_t csp_minsnap_mixed_workspace_bytes(const csp_minsnap_desc *desc);
 
 /* Replaces the time-allocation step of TrajectoryGeneratorTool::GenerateTrajectoryMatrix
  * (minimum_snap.cpp:59-72): T_i = max(|p_{i+1}-p_i| / V_avg, min_time_s), or min_time_s when
- * V_avg <= 1e-6.  Same layouts / descriptor as the solve (path/vel weights ignored). */
+ * V_avg <= 1e-6.  Every operation is rounded on its own in the storage type (no fused multiply-add): with fp64 storage the
+ * times are bit for bit the reference's.  Same layouts / descriptor as the solve (path/vel weights ignored). */
 int csp_minsnap_time_alloc_batch(const csp_minsnap_desc *desc, const void *waypoints, double v_avg,
                                  double min_time_s, void *times, void *hip_stream);
 
@@ -358,7 +359,8 @@ size_t csp_minsnap_plan_workspace_bytes(const csp_minsnap_desc *desc);
  * trajectory at dt = min(0.1, T_seg/10), keeps a point whenever it is >= sample_distance away from
  * the previously kept one, appends the end point, and computes the two statistics the reference
  * prints (max climb/descent rate, min turn radius).
- *   samples : out, [B][capacity][3] (storage dtype); trajectory b uses the first counts[b] rows
+ *   samples : out, [B][capacity][3] (storage dtype); trajectory b uses the first counts[b] rows; the rows from
+ *             min(counts[b], capacity) on are left as they were (every sampler; CSP_MEM_DEVICE)
  *   counts  : out, [B] i32 -- the TRUE number of samples; rows beyond `capacity` are dropped, so
  *             counts[b] > capacity tells the caller to retry with a larger capacity
  *   stats   : optional out, [B][2] f64 = {max climb rate, min turn radius} */

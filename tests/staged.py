@@ -1,7 +1,10 @@
-"""The C-ABI entries that take a caller's workspace, as tables for tests that call them through raw pointers
-(TEST INFRASTRUCTURE ONLY): tests/test_gpu_edges.py (host and device forms bit-equal) and tests/test_gpu_bounds.py
-(guard bands, stale memory, bad lanes)."""
+"""The C-ABI entries as argument tables for tests that call them through raw pointers (TEST INFRASTRUCTURE ONLY):
+tests/test_gpu_edges.py (host and device forms bit-equal), tests/test_gpu_bounds.py (guard bands, stale memory, bad lanes
+of the entries that take a caller's workspace) and tests/test_gpu_bounds_fast.py (the same contracts for the
+workspace-free kernels, the multi-batch entry and the time-allocation / plan / sample / generate chain)."""
 import numpy as np
+
+from tests import guarded
 
 # The five entries that stage host memory the same way: C symbol, workspace function, and per pointer argument
 # (name, "in" / "out", required).  Shapes and element types are in staged_buffers.
@@ -71,3 +74,94 @@ def mixed_buffers(lens, orders, f32, bc_per, seed):
     b.update(orders=np.asarray(orders, dtype=np.int32), coeffs=np.zeros(total_co, io),
              coeff_offsets=np.zeros(len(lens) + 1, np.int64))
     return b
+
+
+# The entries of tests/test_gpu_bounds_fast.py that the tables above do not hold: (C symbol, workspace function or None,
+# arguments).  Scalars of the C signature (v_avg, min_time_s, sample_distance, capacity) are the test's own business.
+FAST_ENTRIES = {
+    "solve_batch": STAGED["solve_batch"],
+    "time_alloc_batch": ("csp_minsnap_time_alloc_batch", None, (("waypoints", "in", True), ("times", "out", True))),
+    "plan_batch": ("csp_minsnap_plan_batch", "csp_minsnap_plan_workspace_bytes",
+                   (("waypoints", "in", True), ("bc", "in", True), ("times", "out", True), ("coeffs", "out", True),
+                    ("max_dev", "out", False), ("vel_zero_weight_out", "out", False), ("iterations", "out", False),
+                    ("status", "out", False))),
+    "sample_batch": ("csp_minsnap_sample_batch", None,
+                     (("times", "in", True), ("coeffs", "in", True), ("samples", "out", True), ("counts", "out", True),
+                      ("stats", "out", False))),
+    "generate_batch": ("csp_minsnap_generate_batch", "csp_minsnap_plan_workspace_bytes",
+                       (("waypoints", "in", True), ("bc", "in", True), ("samples", "out", True), ("counts", "out", True),
+                        ("stats", "out", False), ("times", "out", True), ("coeffs", "out", True), ("max_dev", "out", False),
+                        ("vel_zero_weight_out", "out", False), ("iterations", "out", False), ("status", "out", False))),
+}
+
+
+class Carved:
+    """One pointer argument inside a guarded carve (tests/guarded.py) of exactly its size.  `shift` > 0 puts the argument
+    that many bytes past the carve's (256-byte aligned) start, the carve being that much larger: the lead bytes keep the
+    guard pattern and are checked with the bands.  An input holds `host`'s bytes, an output starts as `fill` bytes."""
+
+    def __init__(self, host, device, name, fill=None, band=guarded.BAND, shift=0):
+        self.host, self.shift, self.name = np.ascontiguousarray(host), int(shift), name
+        self.g = guarded.Guarded(self.host.nbytes + self.shift, device, band, name=name)
+        if self.shift:
+            self.g.raw[:self.shift].fill_(guarded.PATTERN)
+        if fill is None:
+            self.put(self.host)
+        else:
+            self.g.raw[self.shift:].fill_(int(fill))
+
+    def put(self, array):
+        src = np.ascontiguousarray(array)
+        assert src.nbytes == self.host.nbytes, (self.name, src.nbytes, self.host.nbytes)
+        if src.nbytes:
+            import torch
+            self.g.raw[self.shift:].copy_(torch.from_numpy(src.reshape(-1).view(np.uint8).copy()))
+        return self
+
+    def data_ptr(self):
+        return self.g.data_ptr() + self.shift
+
+    def bytes(self):
+        return self.g.bytes()[self.shift:]
+
+    def numpy(self, dtype=None, shape=None):
+        return self.bytes().view(self.host.dtype if dtype is None else dtype).reshape(self.host.shape if shape is None else shape)
+
+    def check(self):
+        self.g.check()
+        lead = self.g.bytes()[:self.shift]
+        assert (lead == guarded.PATTERN).all(), "%s: the %d bytes in front of the shifted pointer were written" % (self.name, self.shift)
+
+
+def carve_args(args, host, opt, fill, device, band=guarded.BAND, shift=None):
+    """({name: Carved} of the inputs, {name: Carved} of the outputs) of an argument table: every input a guarded copy of
+    host[name], every required output -- and, with `opt`, every optional one (`opt` may also be a set of names) -- a
+    guarded array of host[name]'s shape and type that starts as `fill` bytes.  shift: {name: bytes}, see Carved."""
+    shift = shift or {}
+    ins, outs = {}, {}
+    for n, kind, req in args:
+        if kind == "in":
+            ins[n] = Carved(host[n], device, n, None, band, shift.get(n, 0))
+        elif req or (n in opt if isinstance(opt, (set, frozenset)) else opt):
+            outs[n] = Carved(host[n], device, n, fill, band, shift.get(n, 0))
+    return ins, outs
+
+
+def arg_pointers(args, ins, outs):
+    """The pointer arguments in the table's order (None for an optional output that is not passed)."""
+    out = []
+    for n, kind, _ in args:
+        g = ins.get(n) if kind == "in" else outs.get(n)
+        out.append(g.data_ptr() if g is not None else None)
+    return out
+
+
+def check_carves(tag, carves, inputs):
+    """No guard byte of any of `carves` changed, and every one of `inputs` (Carved) still holds its host bytes."""
+    for g in carves:
+        try:
+            g.check()
+        except AssertionError as e:
+            raise AssertionError("%r: %s" % (tag, e)) from None
+    for g in inputs:
+        assert g.bytes().tobytes() == g.host.tobytes(), (tag, "input changed", g.name)

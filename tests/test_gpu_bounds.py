@@ -25,7 +25,8 @@ import pytest
 import torch
 
 from tests import guarded
-from tests.staged import WORKSPACE_ENTRIES, mixed_block_elements, mixed_buffers, staged_buffers
+from tests.staged import (WORKSPACE_ENTRIES, Carved, arg_pointers, carve_args, check_carves, mixed_block_elements, mixed_buffers,
+                          staged_buffers)
 from tests.timeopt_ref import NOT_CONVERGED, cost_grad, optimize
 
 pytestmark = pytest.mark.gpu
@@ -34,8 +35,6 @@ DEV = "cuda:0"
 VW = 0.02                       # the descriptor's vel_zero_weight of every call here
 NONFINITE, NOT_SPD, SKIPPED = 1, 2, 4
 GATE_J = {2: 1e-13, 3: 1e-13, 4: 1e-11, 5: 1e-9}     # tests/test_gpu_timeopt.py: kernel J against tests/timeopt_ref.py
-_TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64, np.dtype(np.int32): torch.int32,
-          np.dtype(np.int64): torch.int64}
 
 # lens: segments per trajectory; uniform: num_segments = lens[0] (else ragged with max_segments); opt: the optional
 # outputs are passed; orders: per trajectory (the mixed entry only)
@@ -123,17 +122,12 @@ def _call(csp, entry, case, host, fill, vw=None, prm=None):
     lib = csp.raw_lib()
     B, ragged = len(case.lens), not case.uniform
     tag = (entry, _case_id(case), hex(fill))
-    ins, outs = {}, {}
-    for n, kind, req in args:
-        if kind == "in":
-            ins[n] = guarded.carve_from(host[n], DEV, name=n)
-        elif req or case.opt:
-            outs[n] = guarded.carve_array(host[n].shape, _TORCH[host[n].dtype], DEV, name=n).fill(fill)
+    ins, outs = carve_args(args, host, case.opt, fill, DEV)
     extra = {}
     if ragged:
-        extra["seg_offsets"] = guarded.carve_from(_offsets(case), DEV, name="seg_offsets")
+        extra["seg_offsets"] = Carved(_offsets(case), DEV, "seg_offsets")
     if vw is not None:
-        extra["vel_zero_weight_per_traj"] = guarded.carve_from(vw, DEV, name="vel_zero_weight_per_traj")
+        extra["vel_zero_weight_per_traj"] = Carved(vw, DEV, "vel_zero_weight_per_traj")
     desc = csp.make_desc(case.order, B, 0 if ragged else case.lens[0], csp.DTYPE_F32 if case.f32 else csp.DTYPE_F64, 0.0, VW,
                          csp.MEM_DEVICE, case.bc_per, extra["seg_offsets"].data_ptr() if ragged else None,
                          case.max_segments if ragged else 0,
@@ -143,25 +137,15 @@ def _call(csp, entry, case, host, fill, vw=None, prm=None):
     ws = guarded.Guarded(need, DEV, name="workspace").fill(fill)
     call = [ctypes.byref(desc)] + ([ctypes.byref(prm if prm is not None else _timeopt_params(csp))]
                                    if entry == "optimize_times_batch" else [])
-    for n, kind, req in args:
-        g = ins.get(n) if kind == "in" else outs.get(n)
-        call.append(g.data_ptr() if g is not None else None)
+    call += arg_pointers(args, ins, outs)
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     rc = getattr(lib, sym)(*call, ws.data_ptr(), need, stream)
     assert rc == 0, (tag, rc, csp.strerror(rc))
     torch.cuda.synchronize()
-    for g in [ws] + list(ins.values()) + list(outs.values()) + list(extra.values()):
-        try:
-            g.check()
-        except AssertionError as e:
-            raise AssertionError("%r (workspace %d bytes): %s" % (tag, need, e)) from None
-    for n, g in ins.items():
-        assert g.bytes().tobytes() == np.ascontiguousarray(host[n]).tobytes(), (tag, "input changed", n)
-    if ragged:
-        assert np.array_equal(extra["seg_offsets"].numpy(np.int64), _offsets(case)), (tag, "seg_offsets changed")
-    if vw is not None:
-        assert extra["vel_zero_weight_per_traj"].bytes().tobytes() == vw.tobytes(), (tag, "weights changed")
-    return {n: g.numpy(host[n].dtype, host[n].shape) for n, g in outs.items()}, need
+    # every band intact; no byte of the inputs, the offsets or the weights changed
+    check_carves((tag, "workspace %d bytes" % need), [ws] + list(ins.values()) + list(outs.values()) + list(extra.values()),
+                 list(ins.values()) + list(extra.values()))
+    return {n: g.numpy() for n, g in outs.items()}, need
 
 
 def _expected_status(entry, case):
