@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = (
     "csp_minsnap_cost_batch", "csp_minsnap_cost_workspace_bytes", "csp_minsnap_optimize_times_batch",
     "csp_minsnap_timeopt_workspace_bytes",
     "csp_minsnap_solve_periodic_batch", "csp_minsnap_periodic_workspace_bytes",
+    "csp_minsnap_solve_periodic_batch_vjp", "csp_minsnap_periodic_vjp_workspace_bytes",
     "csp_minsnap_solve_mixed", "csp_minsnap_mixed_workspace_bytes", "csp_minsnap_solve_multi",
     "csp_minsnap_plan_batch", "csp_minsnap_plan_workspace_bytes", "csp_minsnap_sample_batch",
     "csp_minsnap_generate_batch", "csp_minsnap_sample_capacity",
@@ -130,6 +131,8 @@ _PROTOTYPES = {
     "csp_minsnap_timeopt_workspace_bytes": (_SZ, [_D]),
     "csp_minsnap_solve_periodic_batch": (_I, [_D] + [_P] * 7 + [_SZ, _P]),
     "csp_minsnap_periodic_workspace_bytes": (_SZ, [_D]),
+    "csp_minsnap_solve_periodic_batch_vjp": (_I, [_D] + [_P] * 8 + [_SZ, _P]),
+    "csp_minsnap_periodic_vjp_workspace_bytes": (_SZ, [_D]),
     "csp_minsnap_solve_multi": (_I, [_D, _I] + [_P] * 7),
     "csp_minsnap_solve_mixed": (_I, [_D] + [_P] * 8 + [_SZ, _P]),
     "csp_minsnap_mixed_workspace_bytes": (_SZ, [_D]),
@@ -630,6 +633,111 @@ def solve_periodic_batch(waypoints, times, order=4, vel_zero_weight=0.0, seg_off
     _check(_lib.csp_minsnap_solve_periodic_batch(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(co), p(cost),
                                                  p(grad), p(stt), wsp, need, mem.stream(stream)))
     return PeriodicResult(co, cost, grad, stt)
+
+
+def periodic_vjp_workspace_bytes(desc):
+    return int(_lib.csp_minsnap_periodic_vjp_workspace_bytes(ctypes.byref(desc)))
+
+
+class PeriodicVjpResult:
+    """Gradients of solve_periodic_batch_vjp; a gradient that was not asked for is None."""
+    __slots__ = ("waypoints", "times", "status")
+
+    def __init__(self, waypoints, times, status):
+        self.waypoints, self.times, self.status = waypoints, times, status
+
+
+_PERIODIC_VJP_WANT = ("waypoints", "times")
+
+
+def solve_periodic_batch_vjp(waypoints, times, grad_coeffs, grad_cost=None, order=4, vel_zero_weight=0.0, seg_offsets=None,
+                             max_segments=None, vel_zero_weight_per_traj=None, want=_PERIODIC_VJP_WANT, want_status=False,
+                             workspace=None, stream=None):
+    """Vector-Jacobian product of solve_periodic_batch (csp_minsnap_solve_periodic_batch_vjp): given
+    grad_coeffs = dL/dcoeffs in the layout of that call's coefficients and, optionally, grad_cost = dL/dcost [B], returns
+    PeriodicVjpResult(dL/dwaypoints, dL/dtimes, status) for the names in `want`.  Inputs as in solve_periodic_batch:
+    numpy arrays -> CSP_MEM_HOST, torch CUDA tensors -> CSP_MEM_DEVICE."""
+    want = tuple(want)
+    for w in want:
+        if w not in _PERIODIC_VJP_WANT:
+            raise ValueError("want: a subset of %r" % (_PERIODIC_VJP_WANT,))
+    ci = _CallInputs(waypoints, times, None, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    mem, p = ci.mem, ci.mem.ptr
+    gco = mem.contig(grad_coeffs, ci.io)
+    if mem.mem_space == MEM_DEVICE and gco.data_ptr() % 16:   # the kernel reads it in 16-byte pieces (host memory is staged)
+        gco = gco.clone()
+    n = ci.total * 3 * 2 * int(order)
+    if math.prod(gco.shape) != n:
+        raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % n)
+    gj = None
+    if grad_cost is not None:
+        gj = mem.contig(grad_cost, "f64")
+        if math.prod(gj.shape) != ci.B:
+            raise ValueError("grad_cost must hold %d elements (one per trajectory)" % ci.B)
+    desc = ci.desc(order, ci.checked_bc_per_trajectory(), 0.0, vel_zero_weight)
+    gwp = mem.empty(ci.waypoints.shape, ci.io) if "waypoints" in want else None
+    gtm = mem.empty(ci.times.shape, ci.io) if "times" in want else None
+    stt = mem.empty((ci.B,), "i32") if want_status else None
+    wsp, need = _workspace(mem, workspace, periodic_vjp_workspace_bytes, desc)
+    _check(_lib.csp_minsnap_solve_periodic_batch_vjp(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(gco), p(gj), p(gwp),
+                                                     p(gtm), p(stt), wsp, need, mem.stream(stream)))
+    return PeriodicVjpResult(gwp, gtm, stt)
+
+
+def _make_periodic_autograd_fn():
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class SolvePeriodicFn(torch.autograd.Function):
+        """(coeffs, cost) = solve_periodic_batch(waypoints, times); backward = solve_periodic_batch_vjp for the inputs
+        that need it."""
+
+        @staticmethod
+        def forward(ctx, waypoints, times, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj,
+                    with_cost):
+            r = solve_periodic_batch(waypoints.detach(), times.detach(), order=order, vel_zero_weight=vel_zero_weight,
+                                     seg_offsets=seg_offsets, max_segments=max_segments,
+                                     vel_zero_weight_per_traj=vel_zero_weight_per_traj, want_cost=with_cost)
+            ctx.save_for_backward(waypoints, times, seg_offsets, vel_zero_weight_per_traj)
+            ctx.order, ctx.vel_zero_weight, ctx.max_segments = order, vel_zero_weight, max_segments
+            ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None, not as zeros
+            return (r.coeffs, r.cost) if with_cost else r.coeffs
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_coeffs, grad_cost=None):
+            waypoints, times, seg_offsets, vwp = ctx.saved_tensors
+            need_wp, need_tm = ctx.needs_input_grad[:2]
+            want = tuple(n for n, f in zip(_PERIODIC_VJP_WANT, (need_wp, need_tm)) if f)
+            if not want or (grad_coeffs is None and grad_cost is None):
+                return (None,) * 8
+            if grad_coeffs is None:   # the loss uses the cost alone
+                grad_coeffs = times.new_zeros((math.prod(times.shape), 3, 2 * ctx.order))
+            g = solve_periodic_batch_vjp(waypoints, times, grad_coeffs, grad_cost=grad_cost, order=ctx.order,
+                                         vel_zero_weight=ctx.vel_zero_weight, seg_offsets=seg_offsets,
+                                         max_segments=ctx.max_segments, vel_zero_weight_per_traj=vwp, want=want)
+            gwp = g.waypoints.to(waypoints.dtype) if need_wp else None
+            gtm = g.times.to(times.dtype) if need_tm else None
+            return gwp, gtm, None, None, None, None, None, None
+
+    return SolvePeriodicFn
+
+
+_periodic_autograd_fn = None
+
+
+def solve_periodic_batch_autograd(waypoints, times, order=4, vel_zero_weight=0.0, seg_offsets=None, max_segments=None,
+                                  vel_zero_weight_per_traj=None, with_cost=False):
+    """solve_periodic_batch as a differentiable torch op (CUDA tensors): returns the coefficients, or (coeffs, cost) with
+    `with_cost` -- bit-equal to solve_periodic_batch(...) -- with a grad_fn when waypoints or times require grad.  The
+    backward pass is one csp_minsnap_solve_periodic_batch_vjp for the inputs that need a gradient; grad_cost is passed
+    only when the cost received a cotangent.  First-order only (once_differentiable); no gradient with respect to the
+    weights."""
+    global _periodic_autograd_fn
+    if _periodic_autograd_fn is None:
+        _periodic_autograd_fn = _make_periodic_autograd_fn()
+    return _periodic_autograd_fn.apply(waypoints, times, order, vel_zero_weight, seg_offsets, max_segments,
+                                       vel_zero_weight_per_traj, with_cost)
 
 
 def periodic_time_alloc_batch(waypoints, v_avg, min_time_s, seg_offsets=None):

@@ -7,6 +7,7 @@
 // a set of optional outputs goes through ONE staging helper, Stage (with offsets_ok() and sizes_of()).
 #include "../../include/csp_minsnap.h"
 #include "minsnap_launch.h"
+#include "minsnap_periodic_vjp.h"
 #include "minsnap_hoststage.h"
 #include "minsnap_timealloc.h"
 #include "minsnap_shard_schedule.h"
@@ -668,6 +669,25 @@ int dispatch_periodic(const csp_minsnap_desc *d, const Shape &s, const void *wp,
     a.B = s.B; a.S = s.S; a.order = s.order;
     hipError_t e = csp::launch_periodic(a, s.f32, st);
     if (e != hipSuccess) return hip_fail(e, "periodic kernel launch");
+    return CSP_OK;
+}
+
+// csp_minsnap_solve_periodic_batch_vjp: the periodic solve's scope and layouts.
+size_t periodic_vjp_ws_bytes(const Shape &s) {
+    return align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::periodic_vjp_ws_entries(s.order) * (size_t)s.B * 8, 256);
+}
+
+int dispatch_periodic_vjp(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const void *gco,
+                          const double *gcost, void *gwp, void *gtm, int32_t *status, const int64_t *seg_off,
+                          const double *vw_per, void *ws, hipStream_t st) {
+    csp::PeriodicVjpArgs a{};
+    a.wp = wp; a.times = tm; a.grad_coeffs = gco; a.grad_cost = gcost; a.grad_wp = gwp; a.grad_times = gtm; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.ws = ws; a.vw_per = vw_per;
+    a.vel_zero_weight = d->vel_zero_weight;
+    a.B = s.B; a.S = s.S; a.order = s.order;
+    hipError_t e = csp::launch_periodic_vjp(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, "periodic vjp kernel launch");
     return CSP_OK;
 }
 
@@ -1585,6 +1605,49 @@ int csp_minsnap_solve_periodic_batch(const csp_minsnap_desc *desc, const void *w
     return g.run([&] {
         return dispatch_periodic(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(o_co), g.ptr<double>(o_c), g.ptr(o_g), g.ptr<int32_t>(o_st),
                                  g.ptr<const int64_t>(g.seg_off), g.ptr<const double>(g.vw_per), g.ptr(o_ws), st);
+    });
+}
+
+size_t csp_minsnap_periodic_vjp_workspace_bytes(const csp_minsnap_desc *desc) {
+    Shape s;
+    if (validate_vjp(desc, s) != CSP_OK) return 0;
+    return periodic_vjp_ws_bytes(s);
+}
+
+int csp_minsnap_solve_periodic_batch_vjp(const csp_minsnap_desc *desc, const void *waypoints, const void *times,
+                                         const void *grad_coeffs, const double *grad_cost, void *grad_waypoints,
+                                         void *grad_times, int32_t *status, void *workspace, size_t workspace_bytes,
+                                         void *hip_stream) {
+    Shape s;
+    int rc = validate_vjp(desc, s);
+    if (rc != CSP_OK) return rc;
+    if (s.B == 0) return CSP_OK;
+    if (!waypoints || !times || !grad_coeffs || (!grad_waypoints && !grad_times)) return CSP_ERR_INVALID_ARG;
+    const size_t n_ws = periodic_vjp_ws_bytes(s);
+    if (desc->mem_space == CSP_MEM_DEVICE) {
+        if (n_ws > 0 && (!workspace || workspace_bytes < n_ws)) return CSP_ERR_WORKSPACE;
+        if ((uintptr_t)workspace & 7u) return CSP_ERR_WORKSPACE;
+        if ((uintptr_t)grad_coeffs & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // p_bar records are read as 2-element vectors
+    } else if (!offsets_ok(desc, s)) {
+        return CSP_ERR_INVALID_ARG;
+    }
+    rc = select_device(desc->device_id);
+    if (rc != CSP_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+
+    if (desc->mem_space == CSP_MEM_DEVICE)
+        return dispatch_periodic_vjp(desc, s, waypoints, times, grad_coeffs, grad_cost, grad_waypoints, grad_times, status,
+                                     desc->seg_offsets, desc->vel_zero_weight_per_traj, workspace, st);
+
+    // CSP_MEM_HOST: as csp_minsnap_solve_periodic_batch
+    Stage g(desc, s, st, waypoints, times, nullptr);
+    const size_t o_gc = g.in(grad_coeffs, g.z.co), o_gj = g.in(grad_cost, (size_t)s.B * 8);
+    const size_t o_gw = g.out(grad_waypoints, g.z.wp), o_gt = g.out(grad_times, g.z.tm);
+    const size_t o_st = g.out(status, (size_t)s.B * 4), o_ws = g.hc.scratch(n_ws);
+    return g.run([&] {
+        return dispatch_periodic_vjp(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(o_gc), g.ptr<const double>(o_gj), g.ptr(o_gw),
+                                     g.ptr(o_gt), g.ptr<int32_t>(o_st), g.ptr<const int64_t>(g.seg_off),
+                                     g.ptr<const double>(g.vw_per), g.ptr(o_ws), st);
     });
 }
 

@@ -260,6 +260,39 @@ int csp_minsnap_solve_periodic_batch(const csp_minsnap_desc *desc, const void *w
  * descriptor). */
 size_t csp_minsnap_periodic_workspace_bytes(const csp_minsnap_desc *desc);
 
+/* Reverse mode of csp_minsnap_solve_periodic_batch: given grad_coeffs = dL/dcoeffs and, optionally,
+ * grad_cost = dL/dcost for a scalar L of that call's coefficients and cost, writes dL/dwaypoints and dL/dtimes.  The
+ * adjoint system is the forward's block-cyclic matrix, shared by the three axes; the primal is re-solved from waypoints
+ * and times in the same sweep (the forward's coefficients are not an input).  One lane per trajectory, no atomics, every
+ * sum in a fixed order: two calls give identical bits, whichever outputs are asked for.
+ *   desc           : the scope, layouts (RAGGED LAYOUT included) and CSP_ERR_UNSUPPORTED cases of
+ *                    csp_minsnap_solve_periodic_batch; bc_per_trajectory is ignored
+ *   waypoints      : [B][S][3]
+ *   times          : [B][S]
+ *   grad_coeffs    : [B][S][3][2*order], the layout of coeffs; 16-byte aligned (fp64) / 8-byte (fp32)
+ *   grad_cost      : optional, [B] f64; NULL means 0 (its terms are then not computed)
+ *   grad_waypoints : optional out, the layout and storage type of `waypoints`
+ *   grad_times     : optional out, the layout and storage type of `times`; with grad_cost it includes
+ *                    grad_cost * dJ/dT_j, the forward's grad_times.  CSP_ERR_INVALID_ARG when both outputs are NULL.
+ *                    S = 1: grad_waypoints = sum of grad_coeffs at power 0 per axis, grad_times = 0.
+ *                    A trajectory with S_b = 0 gets status 0; nothing else is written for it.
+ *   status         : optional out, [B] i32: CSP_TRAJ_NOT_SPD (a pivot <= 0, the border's Schur complement included),
+ *                    CSP_TRAJ_NONFINITE (a gradient written for the trajectory is inf/NaN).  A bad trajectory does not
+ *                    change any output of another one.
+ *   workspace      : device scratch of csp_minsnap_periodic_vjp_workspace_bytes(desc) bytes (CSP_MEM_DEVICE, 8-byte
+ *                    aligned); may be NULL/0 with CSP_MEM_HOST.  With o = order, Smax = num_segments (uniform) or
+ *                    max_segments (ragged):
+ *                      round_up_256((Smax - 1) * (2(o-1)^2 + 6(o-1)) * B * 8)
+ * Arguments are checked before a device is looked for.
+ * CSP_MEM_HOST: staged through the cached arena, synchronous.  CSP_MEM_DEVICE: asynchronous on `hip_stream`. */
+int csp_minsnap_solve_periodic_batch_vjp(const csp_minsnap_desc *desc, const void *waypoints, const void *times,
+                                         const void *grad_coeffs, const double *grad_cost, void *grad_waypoints,
+                                         void *grad_times, int32_t *status, void *workspace, size_t workspace_bytes,
+                                         void *hip_stream);
+/* Device scratch bytes csp_minsnap_solve_periodic_batch_vjp needs (formula above; 0 for an invalid or unsupported
+ * descriptor). */
+size_t csp_minsnap_periodic_vjp_workspace_bytes(const csp_minsnap_desc *desc);
+
 /* The same solve spread over `ngpu` devices of this node from ONE process (the reference planner
  * is a single C++ process).  Trajectories are independent
  * (minimum_snap.cpp has no cross-trajectory term), so the batch is cut into `ngpu` contiguous shards, shard g on the
