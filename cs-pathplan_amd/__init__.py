@@ -1126,10 +1126,16 @@ def alt_global_smooth_batch(input_z, xyz, offsets, lambda_smooth=1.0, max_climb_
     return out, solves
 
 
+BEZIER_UNSAMPLEABLE = 2 ** 31 - 1   # CSP_BEZIER_UNSAMPLEABLE (include/csp_bezier.h)
+
+
 def bezier_generate_batch(waypoints, offsets, resolution=1.0, min_radius=1.0, capacity=4096):
     """Batched math_util::Bezier::GenerateTrajectoryMatrix (math_util/bezier.cpp:127-190; include/csp_bezier.h).
     waypoints [total,3] (paths concatenated), offsets [B+1] point prefix sums; numpy (host) or torch CUDA tensors.
-    Returns (samples [B,capacity,3], counts [B])."""
+    Returns (samples [B,capacity,3], counts [B]).  With CUDA tensors the rows at and past min(counts[b], capacity) are
+    zero; with numpy arrays (host memory, staged through the device) they are unspecified.  counts[b] ==
+    BEZIER_UNSAMPLEABLE (INT32_MAX) marks a path with a segment of more than 2^24 samples at this resolution (a garbage
+    coordinate): it is not walked, its rows are unspecified, the other paths are unaffected."""
     mem = _mem(waypoints)
     wp = mem.contig(waypoints, "f64").reshape(-1, 3)
     off = mem.contig(offsets, "i64")

@@ -3,6 +3,9 @@
 // segment's headings and control points (the <= 10-step curvature loop), counts its samples with the reference's
 // accumulated parameter loop, the wave's prefix sum places every segment in the path's sample array, and the lane
 // evaluates again and stores.  Per-segment evaluation, no solve: the parallelism is paths x segments.
+// Loop bounds: the two parameter loops run only for a step of at least kMinStep = 2^-24 (at most 2^24 + 1 trips, and
+// t + step > t for every t <= 1); a smaller positive step -- a garbage coordinate -- is not walked and the path's count
+// is CSP_BEZIER_UNSAMPLEABLE.  The other loops are bounded by the path's point count, 10 and 64.
 #include "../../include/csp_bezier.h"
 #include "../../include/csp_minsnap.h"
 #include "minsnap_hoststage.h"
@@ -22,6 +25,8 @@ struct BezArgs {
 };
 
 struct Seg4 { double p[4][3]; };
+
+constexpr double kMinStep = 1.0 / 16777216.0;   // 2^-24: more samples than that in ONE segment are not a path (csp_bezier.h)
 
 // control points for arm factor k (bezier.cpp:45-51, :97-103)
 __device__ __forceinline__ void place(const double (&a)[3], const double (&d)[3], double ha, double hd, double chord, double k, Seg4 &s) {
@@ -58,6 +63,7 @@ __global__ void __launch_bounds__(64) bezier_kernel(BezArgs a) {
     const double *P = a.wp + p0 * 3;
     double *out = a.samples + b * a.capacity * 3;
     int64_t base = 0;                             // samples of the segments already placed (wave-uniform)
+    bool unsampleable = false;                    // some segment's step is below kMinStep (wave-uniform)
     for (int s0 = 0; s0 < n - 1; s0 += 64) {
         const int i = s0 + lane;
         const bool act = i < n - 1;
@@ -83,12 +89,14 @@ __global__ void __launch_bounds__(64) bezier_kernel(BezArgs a) {
         place(pa, pd, ha, hd, chord, k, sg);
         const double len = hypot(sg.p[2][0] - sg.p[1][0], sg.p[2][1] - sg.p[1][1]) + chord * 2.0 / 3.0;
         const double step = a.resolution / len;
+        const bool walk = step >= kMinStep;       // false also for a zero, negative or NaN step
+        unsampleable = unsampleable || __builtin_amdgcn_ballot_w64(act && ok && step > 0.0 && !walk) != 0;
         // pass 1: how many samples does `for (t = 0; t <= 1; t += step)` produce?  (accumulated, like :110)
         int cnt = 0;
         if (act) {
             if (ok) {
-                if (step > 0.0) { for (double t = 0.0; t <= 1.0; t += step) ++cnt; }
-                else cnt = 0;                     // a non-positive or NaN step would never end: no samples (not reachable with resolution > 0)
+                if (walk) { for (double t = 0.0; t <= 1.0; t += step) ++cnt; }
+                else cnt = 0;                     // a zero or NaN step (infinite or NaN length) gives no samples; a positive one below kMinStep marks the path
                 if (i > 0 && cnt > 0) --cnt;      // segments after the first drop their first sample (:169-171)
             } else {
                 cnt = 1;                          // fallback: the end point (:174-178)
@@ -102,7 +110,7 @@ __global__ void __launch_bounds__(64) bezier_kernel(BezArgs a) {
             if (ok) {
                 int64_t w = my;
                 bool skip = i > 0;
-                for (double t = 0.0; t <= 1.0 && step > 0.0; t += step) {
+                for (double t = 0.0; t <= 1.0 && walk; t += step) {
                     if (skip) { skip = false; continue; }
                     const double u = 1.0 - t;
                     const double w0 = u * u * u, w1 = 3 * u * u * t, w2 = 3 * u * t * t, w3 = t * t * t;
@@ -116,7 +124,7 @@ __global__ void __launch_bounds__(64) bezier_kernel(BezArgs a) {
         }
         base += __shfl(incl, 63, 64);
     }
-    if (lane == 0) a.counts[b] = (int32_t)base;
+    if (lane == 0) a.counts[b] = (unsampleable || base > CSP_BEZIER_UNSAMPLEABLE) ? CSP_BEZIER_UNSAMPLEABLE : (int32_t)base;
 }
 
 }  // namespace

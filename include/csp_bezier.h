@@ -18,7 +18,15 @@
  * Layouts (fp64, row-major): waypoints [total_points][3] -- the paths concatenated; path b owns points
  * offsets[b] .. offsets[b+1]-1 (a path of fewer than 2 points yields no samples, :129-131);
  * samples [batch][capacity][3]; counts [batch] = the TRUE number of samples of each path (rows beyond `capacity`
- * are dropped: counts[b] > capacity tells the caller to retry with a larger capacity).
+ * are dropped: counts[b] > capacity tells the caller to retry with a larger capacity).  Rows at and past
+ * min(counts[b], capacity) are not written: with CSP_MEM_DEVICE they keep what the caller's buffer held.
+ *
+ * A segment whose parameter step resolution / (|p2 - p1|_xy + 2/3 chord) is positive but below 2^-24 -- more than
+ * 16.7 million samples in ONE segment, 400 MB of rows; in practice a garbage coordinate -- is not walked: the path's
+ * counts[b] is CSP_BEZIER_UNSAMPLEABLE ("cannot be sampled at this resolution"; do NOT retry with that capacity) and its
+ * rows are unspecified, but nothing outside its own `capacity` rows is written.  A true count that does not fit in
+ * int32 saturates at the same value.  Every other path of the batch is unaffected.  A segment whose length
+ * estimate is NaN or infinite contributes no samples; one whose chord is NaN contributes its end point, like a short leg.
  */
 #ifndef CSP_BEZIER_H_
 #define CSP_BEZIER_H_
@@ -29,6 +37,8 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+#define CSP_BEZIER_UNSAMPLEABLE INT32_MAX   /* counts[b] of a path with a segment that cannot be sampled at this resolution */
 
 /* resolution: the reference's `sample_distance_override` when > 0, otherwise 1.0 (:133-136) -- pass the effective value.
  * min_radius: BezierConfig::min_radius (default 1.0 = no curvature constraint; Bezier_3D sets 300, uavPathPlanning.cpp:4492-4494).

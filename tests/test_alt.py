@@ -198,3 +198,24 @@ def test_hip_cyclic_reduction_for_one_long_problem(csp, n):
     for k, (pxyz, pelev) in enumerate(ps):
         ref = oracle.alt_optimize(pxyz, pelev, 1.0, 0.5, 50.0, 2.0, banded=True)
         assert np.max(np.abs(got3[off3[k]:off3[k + 1]] - ref)) <= 1e-8 * np.max(np.abs(ref)), (n, k)
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 7, 120])
+def test_mpmath_reference_matches_oracle(n):
+    """tests/alt_ref.py (banded LDL^T in mpmath at 60 digits, the yardstick of tests/test_gpu_alt_contracts.py) against the C
+    oracle on the benign problems and at the gates of test_oracle_matches_numpy; the active-set loop takes the same number
+    of solves, and its tie margin is far above the oracle's error."""
+    from tests import alt_ref
+    rng = np.random.default_rng(n)
+    xyz, elev = _problem(rng, n, with_gaps=n > 3)
+    for (ls, lf, sd, mcr) in [(1.0, 0.5, 50.0, 2.0), (3.0, 2.0, 30.0, 0.5), (1.0, 0.0, 50.0, 2.0)]:
+        if lf == 0.0 and n < 3:
+            continue
+        z = oracle.alt_optimize(xyz, elev, ls, lf, sd, mcr)
+        assert np.allclose(z, alt_ref.optimize(xyz, elev, ls, lf, sd, mcr), rtol=1e-7, atol=1e-6)
+    zin = xyz[:, 2] + 5.0
+    g, k = oracle.alt_global_smooth(zin, xyz, 1.0, 2.0)
+    g2, k2, margin = alt_ref.global_smooth(zin, xyz, 1.0, 2.0)
+    assert k == k2
+    assert np.allclose(g, g2, rtol=1e-6, atol=1e-4)
+    assert margin > 100 * alt_ref.rel_err(g, g2) * np.max(np.abs(g2)), margin
