@@ -211,7 +211,12 @@ __device__ __forceinline__ void chunked_body(const GenericArgs &a, double *lds, 
     // j = my chunk = my position among them
     const int64_t b = bb;
     if (!traj_ok) S = 0;
-    const int nch = S < lpt ? S : lpt;          // chunks in use (S >= 1 for a real trajectory)
+    // chunks in use (S >= 1 for a real trajectory): as few as CMAX segments per chunk allow.  One chunk per segment up to
+    // lpt (the rule until DESIGN.md §17) left a short trajectory in a wide group with single-segment chunks; the interface
+    // solve is then a twisted elimination of the whole system, whose pivot takes Schur carries from BOTH sides, and under
+    // unequal segment times that cancels digits a one-sided sweep keeps (3.0e-4 per power at order 5, S = 17 on 16 lanes)
+    const int need = (S + CMAX - 1) / CMAX;
+    const int nch = need < lpt ? need : lpt;
     const int q = nch > 0 ? S / nch : 0, rem = nch > 0 ? S - q * nch : 0;
     const bool active = j < nch;
     const int c = active ? q + (j < rem ? 1 : 0) : 0;            // my segments: s0 .. s0+c-1

@@ -49,11 +49,34 @@ class _Num:
     def solve(self, K, R):
         if not self.mp:
             return np.linalg.solve(K, R)
-        X = self.mp.zeros(R.rows, R.cols)
-        for ax in range(R.cols):
-            x = self.mp.lu_solve(K, R.column(ax))
-            for i in range(R.rows):
-                X[i, ax] = x[i]
+        # Gaussian elimination with partial pivoting on rows held as lists, all right-hand sides at once, zeros skipped
+        # (the KKT matrix is sparse): the same dense system at the same precision as mpmath's lu_solve per column, at a
+        # fraction of its time
+        n, nr = R.rows, R.cols
+        rows = [[K[i, j] for j in range(n)] + [R[i, a] for a in range(nr)] for i in range(n)]
+        for c in range(n):
+            p = max(range(c, n), key=lambda r: abs(rows[r][c]))
+            rows[c], rows[p] = rows[p], rows[c]
+            piv = rows[c]
+            inv = 1 / piv[c]
+            nz = [k for k in range(c + 1, n + nr) if piv[k] != 0]
+            for r in range(c + 1, n):
+                rr = rows[r]
+                if rr[c] != 0:
+                    f = rr[c] * inv
+                    for k in nz:
+                        rr[k] -= f * piv[k]
+        X = self.mp.zeros(n, nr)
+        for a in range(nr):
+            x = [None] * n
+            for r in range(n - 1, -1, -1):
+                rr = rows[r]
+                s = rr[n + a]
+                for k in range(r + 1, n):
+                    if rr[k] != 0:
+                        s -= rr[k] * x[k]
+                x[r] = s / rr[r]
+                X[r, a] = x[r]
         return X
 
 

@@ -3,6 +3,8 @@
 seed = 20260501 + config_id; counter-based Philox generator so every rank / device / CPU
 baseline sees bit-identical inputs.  Waypoints: random walk p_{k+1} = p_k + N(0,1)^3 from
 p_0 ~ U(-10,10)^3; segment times ~ U(0.5, 2.0) (well-scaled: cond(R_PP) ~ 5e5 at S=16, o=4).
+The ratio R = max T / min T inside one trajectory is therefore at most 4 in everything drawn here; the tests of unequal
+segment times (R = 16, and 256 for constant-speed legs) draw theirs from tests/spread_ref.py.
 """
 import json
 import os
