@@ -45,6 +45,7 @@ TIMEOPT_FIXED_TOTAL, TIMEOPT_TIME_PENALTY = 0, 1
 EXPORTED_SYMBOLS = (
     "csp_minsnap_solve_batch", "csp_minsnap_solve_batch_sharded", "csp_minsnap_workspace_bytes", "csp_minsnap_time_alloc_batch",
     "csp_minsnap_solve_batch_vjp", "csp_minsnap_vjp_workspace_bytes",
+    "csp_minsnap_solve_batch_cost_vjp", "csp_minsnap_cost_vjp_workspace_bytes",
     "csp_minsnap_cost_batch", "csp_minsnap_cost_workspace_bytes", "csp_minsnap_optimize_times_batch",
     "csp_minsnap_timeopt_workspace_bytes",
     "csp_minsnap_solve_periodic_batch", "csp_minsnap_periodic_workspace_bytes",
@@ -125,6 +126,8 @@ _PROTOTYPES = {
     "csp_minsnap_workspace_bytes": (_SZ, [_D]),
     "csp_minsnap_solve_batch_vjp": (_I, [_D] + [_P] * 9 + [_SZ, _P]),
     "csp_minsnap_vjp_workspace_bytes": (_SZ, [_D]),
+    "csp_minsnap_solve_batch_cost_vjp": (_I, [_D] + [_P] * 10 + [_SZ, _P]),
+    "csp_minsnap_cost_vjp_workspace_bytes": (_SZ, [_D, _I]),
     "csp_minsnap_cost_batch": (_I, [_D] + [_P] * 7 + [_SZ, _P]),
     "csp_minsnap_cost_workspace_bytes": (_SZ, [_D]),
     "csp_minsnap_optimize_times_batch": (_I, [_D, ctypes.POINTER(TimeOptParams)] + [_P] * 9 + [_SZ, _P]),
@@ -437,6 +440,10 @@ def vjp_workspace_bytes(desc):
     return int(_lib.csp_minsnap_vjp_workspace_bytes(ctypes.byref(desc)))
 
 
+def cost_vjp_workspace_bytes(desc, with_grad_coeffs=True):
+    return int(_lib.csp_minsnap_cost_vjp_workspace_bytes(ctypes.byref(desc), 1 if with_grad_coeffs else 0))
+
+
 class VjpResult:
     """Gradients of solve_batch_vjp; a gradient that was not asked for is None."""
     __slots__ = ("waypoints", "times", "bc", "status")
@@ -450,33 +457,49 @@ _VJP_WANT = ("waypoints", "times", "bc")
 
 def solve_batch_vjp(waypoints, times, grad_coeffs, bc=None, order=4, vel_zero_weight=0.0, seg_offsets=None,
                     max_segments=None, vel_zero_weight_per_traj=None, want=_VJP_WANT, want_status=False,
-                    workspace=None, stream=None):
+                    workspace=None, stream=None, grad_cost=None):
     """Vector-Jacobian product of solve_batch (csp_minsnap_solve_batch_vjp): given grad_coeffs = dL/dcoeffs in the layout
     of solve_batch's coefficients, returns VjpResult(dL/dwaypoints, dL/dtimes, dL/dbc, status) for the names in `want`.
     Inputs as in solve_batch (no path penalty): numpy arrays -> CSP_MEM_HOST, torch CUDA tensors -> CSP_MEM_DEVICE.
     dL/dbc has the shape of bc after reshaping to [-1,4,3]: [1,4,3] summed over the batch, or [B,4,3]; bc=None is
-    treated as a shared zero bc."""
+    treated as a shared zero bc.
+    grad_cost = dL/dcost [B] (the cost of snap_cost_batch at the same inputs) adds the cost's cotangent
+    (csp_minsnap_solve_batch_cost_vjp); grad_coeffs may then be None: the cost-only kernel, which needs
+    no adjoint solve and reads no coefficient cotangent."""
     want = tuple(want)
     for w in want:
         if w not in _VJP_WANT:
             raise ValueError("want: a subset of %r" % (_VJP_WANT,))
     ci = _CallInputs(waypoints, times, bc, seg_offsets, max_segments, vel_zero_weight_per_traj)
     mem, p = ci.mem, ci.mem.ptr
-    gco = mem.contig(grad_coeffs, ci.io)
-    if mem.mem_space == MEM_DEVICE and gco.data_ptr() % 16:   # the kernel reads it in 16-byte pieces (host memory is staged)
-        gco = gco.clone()
-    n = ci.total * 3 * 2 * int(order)
-    if math.prod(gco.shape) != n:
-        raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % n)
+    gco = gj = None
+    if grad_coeffs is not None:
+        gco = mem.contig(grad_coeffs, ci.io)
+        if mem.mem_space == MEM_DEVICE and gco.data_ptr() % 16:   # the kernel reads it in 16-byte pieces (host memory is staged)
+            gco = gco.clone()
+        n = ci.total * 3 * 2 * int(order)
+        if math.prod(gco.shape) != n:
+            raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % n)
+    elif grad_cost is None:
+        raise ValueError("grad_coeffs may be None only with a grad_cost")
+    if grad_cost is not None:
+        gj = mem.contig(grad_cost, "f64")
+        if math.prod(gj.shape) != ci.B:
+            raise ValueError("grad_cost must hold %d elements (one per trajectory)" % ci.B)
     # B == 1 counts as per trajectory here: the library sizes the workspace and picks the bc reduction from this flag
     desc = ci.desc(order, ci.checked_bc_per_trajectory(), 0.0, vel_zero_weight)
     gwp = mem.empty(ci.waypoints.shape, ci.io) if "waypoints" in want else None
     gtm = mem.empty(ci.times.shape, ci.io) if "times" in want else None
     gbc = mem.empty(ci.bc.shape, ci.io) if "bc" in want else None
     stt = mem.empty((ci.B,), "i32") if want_status else None
-    wsp, need = _workspace(mem, workspace, vjp_workspace_bytes, desc)
-    _check(_lib.csp_minsnap_solve_batch_vjp(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(ci.bc), p(gco), p(gwp), p(gtm),
-                                            p(gbc), p(stt), wsp, need, mem.stream(stream)))
+    if gj is None:
+        wsp, need = _workspace(mem, workspace, vjp_workspace_bytes, desc)
+        _check(_lib.csp_minsnap_solve_batch_vjp(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(ci.bc), p(gco), p(gwp),
+                                                p(gtm), p(gbc), p(stt), wsp, need, mem.stream(stream)))
+    else:
+        wsp, need = _workspace(mem, workspace, cost_vjp_workspace_bytes, desc, gco is not None)
+        _check(_lib.csp_minsnap_solve_batch_cost_vjp(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(ci.bc), p(gco), p(gj),
+                                                     p(gwp), p(gtm), p(gbc), p(stt), wsp, need, mem.stream(stream)))
     return VjpResult(gwp, gtm, gbc, stt)
 
 
@@ -485,32 +508,39 @@ def _make_autograd_fn():
     from torch.autograd.function import once_differentiable
 
     class SolveBatchFn(torch.autograd.Function):
-        """coeffs = solve_batch(waypoints, times, bc); backward = solve_batch_vjp for the inputs that need it."""
+        """coeffs (or coeffs, cost) = solve_batch (and snap_cost_batch) of (waypoints, times, bc); backward = one
+        solve_batch_vjp for the inputs that need it."""
 
         @staticmethod
-        def forward(ctx, waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj):
-            r = solve_batch(waypoints.detach(), times.detach(), None if bc is None else bc.detach(), order=order,
-                            vel_zero_weight=vel_zero_weight, seg_offsets=seg_offsets, max_segments=max_segments,
-                            vel_zero_weight_per_traj=vel_zero_weight_per_traj)
+        def forward(ctx, waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj,
+                    with_cost):
+            kw = dict(order=order, vel_zero_weight=vel_zero_weight, seg_offsets=seg_offsets, max_segments=max_segments,
+                      vel_zero_weight_per_traj=vel_zero_weight_per_traj)
+            wp, tm, bcd = waypoints.detach(), times.detach(), None if bc is None else bc.detach()
+            r = solve_batch(wp, tm, bcd, **kw)
             ctx.save_for_backward(waypoints, times, bc, seg_offsets, vel_zero_weight_per_traj)
             ctx.order, ctx.vel_zero_weight, ctx.max_segments = order, vel_zero_weight, max_segments
-            return r.coeffs
+            if not with_cost:
+                return r.coeffs
+            ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None, not as zeros
+            return r.coeffs, snap_cost_batch(wp, tm, bcd, want_grad=False, **kw).cost
 
         @staticmethod
         @once_differentiable
-        def backward(ctx, grad_coeffs):
+        def backward(ctx, grad_coeffs, grad_cost=None):
             waypoints, times, bc, seg_offsets, vwp = ctx.saved_tensors
             need_wp, need_tm, need_bc = ctx.needs_input_grad[:3]
             want = tuple(n for n, f in zip(_VJP_WANT, (need_wp, need_tm, need_bc)) if f)
-            if not want:
-                return (None,) * 8
+            if not want or (grad_coeffs is None and grad_cost is None):
+                return (None,) * 9
+            kw = {} if grad_cost is None else {"grad_cost": grad_cost}   # the cost alone: grad_coeffs stays None
             g = solve_batch_vjp(waypoints, times, grad_coeffs, bc=bc, order=ctx.order, vel_zero_weight=ctx.vel_zero_weight,
                                 seg_offsets=seg_offsets, max_segments=ctx.max_segments, vel_zero_weight_per_traj=vwp,
-                                want=want)
+                                want=want, **kw)
             gwp = g.waypoints.to(waypoints.dtype) if need_wp else None
             gtm = g.times.to(times.dtype) if need_tm else None
             gbc = g.bc.reshape(bc.shape).to(bc.dtype) if need_bc else None
-            return gwp, gtm, gbc, None, None, None, None, None
+            return gwp, gtm, gbc, None, None, None, None, None, None
 
     return SolveBatchFn
 
@@ -519,16 +549,19 @@ _autograd_fn = None
 
 
 def solve_batch_autograd(waypoints, times, bc=None, order=4, vel_zero_weight=0.0, seg_offsets=None, max_segments=None,
-                         vel_zero_weight_per_traj=None):
+                         vel_zero_weight_per_traj=None, with_cost=False):
     """solve_batch as a differentiable torch op (CUDA tensors): returns the coefficients -- bit-equal to
     solve_batch(...).coeffs -- with a grad_fn when waypoints, times or bc require grad.  The backward pass is
     csp_minsnap_solve_batch_vjp for the inputs that need a gradient; it is first-order only (once_differentiable).
-    No path penalty; no gradient with respect to the weights."""
+    No path penalty; no gradient with respect to the weights.
+    with_cost: returns (coeffs, cost), the cost bit-equal to snap_cost_batch(...).cost.  The backward pass is then one
+    csp_minsnap_solve_batch_cost_vjp with the cotangents that arrived; a loss on the cost alone runs the cost-only
+    kernel (no adjoint solve, no zero coefficient cotangent is allocated)."""
     global _autograd_fn
     if _autograd_fn is None:
         _autograd_fn = _make_autograd_fn()
     return _autograd_fn.apply(waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments,
-                              vel_zero_weight_per_traj)
+                              vel_zero_weight_per_traj, with_cost)
 
 
 def cost_workspace_bytes(desc):

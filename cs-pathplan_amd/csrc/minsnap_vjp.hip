@@ -18,65 +18,12 @@
 // the per-workgroup partials), so results are bit-identical run to run; no atomics.
 #include "minsnap_device.h"
 #include "minsnap_launch.h"
+#include "minsnap_cost_vjp.h"
+#include "minsnap_vjp_device.h"
 
 namespace csp {
 
-namespace {
-
-template <typename IO, typename R>
-__device__ __forceinline__ void vload3(const IO *p, R (&v)[3]) { v[0] = R(p[0]); v[1] = R(p[1]); v[2] = R(p[2]); }
-
-// One segment's p_bar record [3][2O] as 16-byte (f64) or 8-byte (f32) vector loads: record bases are multiples of
-// 2O*sizeof(IO) bytes from a 16-byte (f64) / 8-byte (f32) aligned array (checked by the C-ABI).
-template <int O, typename IO, typename R>
-__device__ __forceinline__ void load_rec(const IO *src, R (&q)[3][2 * O]) {
-    typedef IO vec2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax)
-#pragma unroll
-        for (int i = 0; i < 2 * O; i += 2) {
-            const vec2 v = *reinterpret_cast<const vec2 *>(src + ax * 2 * O + i);
-            q[ax][i] = R(v.x);
-            q[ax][i + 1] = R(v.y);
-        }
-}
-
-// d_bar[a] = T^deriv_a sum_i G[i][a] T^-pow_i p_bar[i]  (= M(T)^-T p_bar), for the slots a in [A0, A1)
-template <int O, int A0, int A1, typename R>
-__device__ __forceinline__ void dbar_axis(const R (&pb)[2 * O], const R (&tp)[O], const R (&ip)[2 * O], R (&db)[2 * O]) {
-    constexpr int M = 2 * O;
-    R ph[M];
-#pragma unroll
-    for (int i = 0; i < M; ++i) ph[i] = pb[i] * ip[M - 1 - i];
-#pragma unroll
-    for (int a = A0; a < A1; ++a) {
-        R acc = R(0);
-#pragma unroll
-        for (int i = 0; i < M; ++i) {
-            constexpr double zero = 0.0;
-            if (Tab<O>::G(i, a) != zero) acc = fma_<R>(R(Tab<O>::G(i, a)), ph[i], acc);
-        }
-        db[a] = acc * tp[a % O];
-    }
-}
-
-template <int O, typename R> __device__ __forceinline__ void powers(R T, R (&tp)[O], R (&ip)[2 * O]) {
-    tp[0] = R(1);
-#pragma unroll
-    for (int e = 1; e < O; ++e) tp[e] = tp[e - 1] * T;
-    ip[0] = R(1);
-    ip[1] = fast_rcp(T);
-#pragma unroll
-    for (int e = 2; e < 2 * O; ++e) ip[e] = ip[e - 1] * ip[1];
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-}  // namespace
+using namespace vjpk;   // minsnap_vjp_device.h: vload3, load_rec, dbar_axis, powers, wave_sum
 
 template <int O, typename IO, typename R>
 __global__ void __launch_bounds__(64) minsnap_vjp_kernel(VjpArgs a) {
@@ -425,6 +372,12 @@ template <typename IO> static hipError_t launch_vjp_r(const VjpArgs &a, hipStrea
         case 5: return launch_vjp_o<5, IO>(a, st);
     }
     return hipErrorInvalidValue;
+}
+
+hipError_t launch_vjp_bc_reduce(const double *part, int64_t nblk, void *grad_bc, bool f32, hipStream_t st) {
+    if (f32) hipLaunchKernelGGL((minsnap_vjp_bc_reduce<float, double>), dim3(1), dim3(64), 0, st, part, nblk, (float *)grad_bc);
+    else hipLaunchKernelGGL((minsnap_vjp_bc_reduce<double, double>), dim3(1), dim3(64), 0, st, part, nblk, (double *)grad_bc);
+    return hipGetLastError();
 }
 
 hipError_t launch_vjp(const VjpArgs &a, bool f32, hipStream_t st) {

@@ -163,6 +163,41 @@ int csp_minsnap_solve_batch_vjp(const csp_minsnap_desc *desc, const void *waypoi
  * descriptor). */
 size_t csp_minsnap_vjp_workspace_bytes(const csp_minsnap_desc *desc);
 
+/* Reverse mode of (coeffs, J) = csp_minsnap_solve_batch + csp_minsnap_cost_batch: csp_minsnap_solve_batch_vjp with a
+ * second cotangent grad_cost = dL/dJ.  J is the snap cost of csp_minsnap_cost_batch at the optimum; by
+ * the envelope theorem its part of the gradients needs no adjoint solve:
+ *   dJ/dwaypoints, dJ/dbc = 2 (K d) at the fixed slots      (+ 2 w v at the two boundary velocities)
+ *   dJ/dtimes             = csp_minsnap_cost_batch's grad_times
+ * so with grad_coeffs NULL the call is the cost kernel's three-column sweep plus a few products per segment, and
+ * grad_coeffs is never read.  With both cotangents it is the VJP's six-column sweep with the J terms added in the back
+ * substitution.  Deterministic run to run (no atomics).
+ *   desc          : the scope and CSP_ERR_UNSUPPORTED cases of csp_minsnap_solve_batch_vjp
+ *   grad_coeffs   : [B][S][3][2*order] as for csp_minsnap_solve_batch_vjp, or NULL (no cotangent on the coefficients)
+ *   grad_cost     : [B] f64 (whatever the storage type), or NULL: then the call IS csp_minsnap_solve_batch_vjp (same
+ *                   kernel, same bits).  Both NULL: CSP_ERR_INVALID_ARG.
+ *   grad_waypoints, grad_times, grad_bc : optional outs as for csp_minsnap_solve_batch_vjp; all three NULL:
+ *                   CSP_ERR_INVALID_ARG
+ *   status        : optional [B] i32: CSP_TRAJ_NOT_SPD (a pivot <= 0), CSP_TRAJ_NONFINITE (a gradient this trajectory
+ *                   writes is inf/NaN, e.g. from an infinite grad_cost entry)
+ *   workspace     : device scratch of csp_minsnap_cost_vjp_workspace_bytes(desc, grad_coeffs != NULL) bytes
+ *                   (CSP_MEM_DEVICE, 8-byte aligned); may be NULL/0 with CSP_MEM_HOST.  With o = order, Smax =
+ *                   num_segments (uniform) or max_segments (ragged), c = 6 with grad_coeffs and 3 without:
+ *                     round_up_256((Smax - 1) * ((o-1)^2 + c(o-1)) * B * 8)
+ *                       + (bc_per_trajectory ? 0 : 12 * ceil(B / 64) * 8)
+ *                   (c = 6 is csp_minsnap_vjp_workspace_bytes, c = 3 the factors of csp_minsnap_cost_workspace_bytes;
+ *                   the second term holds the per-workgroup partials of a shared bc's gradient and is only written
+ *                   when grad_bc is asked for)
+ * Every argument check (workspace size and alignment of a device-memory call included) comes back before a device is
+ * looked for.  CSP_MEM_HOST: staged through the cached arena, synchronous.  CSP_MEM_DEVICE: asynchronous on
+ * `hip_stream`. */
+int csp_minsnap_solve_batch_cost_vjp(const csp_minsnap_desc *desc, const void *waypoints, const void *times,
+                                     const void *bc, const void *grad_coeffs, const double *grad_cost,
+                                     void *grad_waypoints, void *grad_times, void *grad_bc, int32_t *status,
+                                     void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Device scratch bytes csp_minsnap_solve_batch_cost_vjp needs for `desc`, with (non-zero) or without (0) a grad_coeffs
+ * cotangent (formula above; 0 for an invalid or unsupported descriptor). */
+size_t csp_minsnap_cost_vjp_workspace_bytes(const csp_minsnap_desc *desc, int with_grad_coeffs);
+
 /* The cost the solve minimises and its gradient with respect to the segment times:
  *   J(T)    = sum_axes sum_j [ integral_0^T_j (p_j^(order))^2 dt + w (v_j(0)^2 + v_j(T_j)^2) ]   at the solve's optimum
  *   dJ/dT_j = (1/T_j) sum_axes sum_ab (deriv_a + deriv_b + 1 - 2 order) Qt_ab(T_j) d_a d_b   (envelope theorem: the
