@@ -8,7 +8,7 @@
 #include "../../include/csp_minsnap.h"
 #include "minsnap_launch.h"
 #include "minsnap_periodic_vjp.h"
-#include "minsnap_cost_vjp.h"
+#include "minsnap_vjp.h"
 #include "minsnap_hoststage.h"
 #include "minsnap_timealloc.h"
 #include "minsnap_shard_schedule.h"
@@ -551,65 +551,37 @@ int validate_vjp(const csp_minsnap_desc *d, Shape &s) {
     return CSP_OK;
 }
 
-size_t vjp_ws_bytes(const csp_minsnap_desc *d, const Shape &s, size_t *part_off) {
-    const size_t factors = align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::vjp_ws_entries(s.order) * (size_t)s.B * 8, 256);
-    if (part_off) *part_off = factors;
-    return factors + (d->bc_per_trajectory ? 0 : 12 * (size_t)csp::vjp_blocks(s.B) * 8);
-}
-
-int dispatch_vjp(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const void *bc, const void *gco,
-                 void *gwp, void *gtm, void *gbc, int32_t *status, const int64_t *seg_off, const double *vw_per, void *ws,
-                 size_t ws_size, hipStream_t st) {
-    size_t part_off = 0;
-    const size_t need = vjp_ws_bytes(d, s, &part_off);
-    if (need > 0 && (!ws || ws_size < need)) return CSP_ERR_WORKSPACE;
-    if ((uintptr_t)ws & 7u) return CSP_ERR_WORKSPACE;
-    if ((uintptr_t)gco & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // p_bar records are read as 2-element vectors
-    csp::VjpArgs a;
-    a.wp = wp; a.times = tm; a.bc = bc; a.grad_coeffs = gco;
-    a.grad_wp = gwp; a.grad_times = gtm; a.grad_bc = gbc; a.status = status;
-    a.seg_off = s.ragged ? seg_off : nullptr;
-    a.ws = ws;
-    a.bc_part = (gbc && !d->bc_per_trajectory) ? (void *)((char *)ws + part_off) : nullptr;
-    a.vw_per = vw_per;
-    a.vel_zero_weight = d->vel_zero_weight;
-    a.B = s.B; a.S = s.S; a.order = s.order; a.bc_per_traj = d->bc_per_trajectory ? 1 : 0;
-    hipError_t e = csp::launch_vjp(a, s.f32, st);
-    if (e != hipSuccess) return hip_fail(e, "vjp kernel launch");
-    return CSP_OK;
-}
-
 // csp_minsnap_cost_batch / csp_minsnap_optimize_times_batch: the VJP's scope (validate_vjp).
 size_t cost_ws_bytes(const Shape &s) {
     return align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * csp::timeopt_ws_entries(s.order) * (size_t)s.B * 8, 256);
 }
 
-// csp_minsnap_solve_batch_cost_vjp: the VJP's workspace with a grad_coeffs cotangent; without one the cost kernel's
-// factors plus the VJP's partials of a shared bc's gradient.
-size_t cost_vjp_ws_bytes(const csp_minsnap_desc *d, const Shape &s, bool pbar, size_t *part_off) {
-    if (pbar) return vjp_ws_bytes(d, s, part_off);
-    const size_t factors = cost_ws_bytes(s);
+// csp_minsnap_solve_batch_vjp / _cost_vjp: the factors with six right-hand-side columns under a grad_coeffs cotangent
+// (pbar), without one the cost kernel's three; then the partials of a shared bc's gradient.
+size_t vjp_ws_bytes(const csp_minsnap_desc *d, const Shape &s, bool pbar, size_t *part_off) {
+    const size_t entries = pbar ? csp::vjp_ws_entries(s.order) : csp::timeopt_ws_entries(s.order);
+    const size_t factors = align_up((size_t)(s.Smax > 1 ? s.Smax - 1 : 0) * entries * (size_t)s.B * 8, 256);
     if (part_off) *part_off = factors;
     return factors + (d->bc_per_trajectory ? 0 : 12 * (size_t)csp::vjp_blocks(s.B) * 8);
 }
 
 // workspace and alignment of a device-memory call, from the pointers' values alone
-int check_cost_vjp_device_args(const csp_minsnap_desc *d, const Shape &s, const void *gco, const void *ws, size_t ws_size) {
-    const size_t need = cost_vjp_ws_bytes(d, s, gco != nullptr, nullptr);
+int check_vjp_device_args(const csp_minsnap_desc *d, const Shape &s, const void *gco, const void *ws, size_t ws_size) {
+    const size_t need = vjp_ws_bytes(d, s, gco != nullptr, nullptr);
     if (need > 0 && (!ws || ws_size < need)) return CSP_ERR_WORKSPACE;
     if ((uintptr_t)ws & 7u) return CSP_ERR_WORKSPACE;
     if ((uintptr_t)gco & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // p_bar records are read as 2-element vectors
     return CSP_OK;
 }
 
-int dispatch_cost_vjp(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const void *bc, const void *gco,
-                      const double *gcost, void *gwp, void *gtm, void *gbc, int32_t *status, const int64_t *seg_off,
-                      const double *vw_per, void *ws, size_t ws_size, hipStream_t st) {
-    if (!gcost) return dispatch_vjp(d, s, wp, tm, bc, gco, gwp, gtm, gbc, status, seg_off, vw_per, ws, ws_size, st);
-    int rc = check_cost_vjp_device_args(d, s, gco, ws, ws_size);
+// gco or gcost may be null (not both): the kernel is compiled for the cotangents that are given
+int dispatch_vjp(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const void *bc, const void *gco,
+                 const double *gcost, void *gwp, void *gtm, void *gbc, int32_t *status, const int64_t *seg_off,
+                 const double *vw_per, void *ws, size_t ws_size, hipStream_t st) {
+    int rc = check_vjp_device_args(d, s, gco, ws, ws_size);
     if (rc != CSP_OK) return rc;
     size_t part_off = 0;
-    (void)cost_vjp_ws_bytes(d, s, gco != nullptr, &part_off);
+    (void)vjp_ws_bytes(d, s, gco != nullptr, &part_off);
     csp::CostVjpArgs a;
     a.wp = wp; a.times = tm; a.bc = bc; a.grad_coeffs = gco; a.grad_cost = gcost;
     a.grad_wp = gwp; a.grad_times = gtm; a.grad_bc = gbc; a.status = status;
@@ -619,8 +591,8 @@ int dispatch_cost_vjp(const csp_minsnap_desc *d, const Shape &s, const void *wp,
     a.vw_per = vw_per;
     a.vel_zero_weight = d->vel_zero_weight;
     a.B = s.B; a.S = s.S; a.order = s.order; a.bc_per_traj = d->bc_per_trajectory ? 1 : 0;
-    hipError_t e = csp::launch_cost_vjp(a, s.f32, st);
-    if (e != hipSuccess) return hip_fail(e, "cost vjp kernel launch");
+    hipError_t e = csp::launch_vjp(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, gcost ? "cost vjp kernel launch" : "vjp kernel launch");
     return CSP_OK;
 }
 
@@ -1502,7 +1474,7 @@ void csp_minsnap_release_cached_memory(void) { csp::arena_free_idle(); }
 size_t csp_minsnap_vjp_workspace_bytes(const csp_minsnap_desc *desc) {
     Shape s;
     if (validate_vjp(desc, s) != CSP_OK) return 0;
-    return vjp_ws_bytes(desc, s, nullptr);
+    return vjp_ws_bytes(desc, s, true, nullptr);
 }
 
 int csp_minsnap_solve_batch_vjp(const csp_minsnap_desc *desc, const void *waypoints, const void *times,
@@ -1519,18 +1491,18 @@ int csp_minsnap_solve_batch_vjp(const csp_minsnap_desc *desc, const void *waypoi
     hipStream_t st = (hipStream_t)hip_stream;
 
     if (desc->mem_space == CSP_MEM_DEVICE)
-        return dispatch_vjp(desc, s, waypoints, times, bc, grad_coeffs, grad_waypoints, grad_times, grad_bc, status,
+        return dispatch_vjp(desc, s, waypoints, times, bc, grad_coeffs, nullptr, grad_waypoints, grad_times, grad_bc, status,
                             desc->seg_offsets, desc->vel_zero_weight_per_traj, workspace, workspace_bytes, st);
 
     // CSP_MEM_HOST: staged through the cached arena, synchronous (as csp_minsnap_solve_batch)
     if (!offsets_ok(desc, s)) return CSP_ERR_INVALID_ARG;
-    const size_t n_ws = vjp_ws_bytes(desc, s, nullptr);
+    const size_t n_ws = vjp_ws_bytes(desc, s, true, nullptr);
     Stage g(desc, s, st, waypoints, times, bc);
     const size_t o_gc = g.in(grad_coeffs, g.z.co);
     const size_t o_gw = g.out(grad_waypoints, g.z.wp), o_gt = g.out(grad_times, g.z.tm), o_gb = g.out(grad_bc, g.z.bc);
     const size_t o_st = g.out(status, (size_t)s.B * 4), o_ws = g.hc.scratch(n_ws);
     return g.run([&] {
-        return dispatch_vjp(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(g.bc), g.ptr(o_gc), g.ptr(o_gw), g.ptr(o_gt), g.ptr(o_gb),
+        return dispatch_vjp(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(g.bc), g.ptr(o_gc), nullptr, g.ptr(o_gw), g.ptr(o_gt), g.ptr(o_gb),
                             g.ptr<int32_t>(o_st), g.ptr<const int64_t>(g.seg_off), g.ptr<const double>(g.vw_per), g.ptr(o_ws), n_ws, st);
     });
 }
@@ -1538,7 +1510,7 @@ int csp_minsnap_solve_batch_vjp(const csp_minsnap_desc *desc, const void *waypoi
 size_t csp_minsnap_cost_vjp_workspace_bytes(const csp_minsnap_desc *desc, int with_grad_coeffs) {
     Shape s;
     if (validate_vjp(desc, s) != CSP_OK) return 0;
-    return cost_vjp_ws_bytes(desc, s, with_grad_coeffs != 0, nullptr);
+    return vjp_ws_bytes(desc, s, with_grad_coeffs != 0, nullptr);
 }
 
 int csp_minsnap_solve_batch_cost_vjp(const csp_minsnap_desc *desc, const void *waypoints, const void *times,
@@ -1552,7 +1524,7 @@ int csp_minsnap_solve_batch_cost_vjp(const csp_minsnap_desc *desc, const void *w
     if (!waypoints || !times || !bc || (!grad_coeffs && !grad_cost)) return CSP_ERR_INVALID_ARG;
     if (!grad_waypoints && !grad_times && !grad_bc) return CSP_ERR_INVALID_ARG;
     if (desc->mem_space == CSP_MEM_DEVICE) {   // checked from the pointers' values, before a device is looked for
-        rc = check_cost_vjp_device_args(desc, s, grad_coeffs, workspace, workspace_bytes);
+        rc = check_vjp_device_args(desc, s, grad_coeffs, workspace, workspace_bytes);
         if (rc != CSP_OK) return rc;
     } else if (!offsets_ok(desc, s)) {
         return CSP_ERR_INVALID_ARG;
@@ -1562,19 +1534,19 @@ int csp_minsnap_solve_batch_cost_vjp(const csp_minsnap_desc *desc, const void *w
     hipStream_t st = (hipStream_t)hip_stream;
 
     if (desc->mem_space == CSP_MEM_DEVICE)
-        return dispatch_cost_vjp(desc, s, waypoints, times, bc, grad_coeffs, grad_cost, grad_waypoints, grad_times, grad_bc,
-                                 status, desc->seg_offsets, desc->vel_zero_weight_per_traj, workspace, workspace_bytes, st);
+        return dispatch_vjp(desc, s, waypoints, times, bc, grad_coeffs, grad_cost, grad_waypoints, grad_times, grad_bc,
+                            status, desc->seg_offsets, desc->vel_zero_weight_per_traj, workspace, workspace_bytes, st);
 
     // CSP_MEM_HOST: as csp_minsnap_solve_batch_vjp; a cotangent that is not given is not staged
-    const size_t n_ws = cost_vjp_ws_bytes(desc, s, grad_coeffs != nullptr, nullptr);
+    const size_t n_ws = vjp_ws_bytes(desc, s, grad_coeffs != nullptr, nullptr);
     Stage g(desc, s, st, waypoints, times, bc);
     const size_t o_gc = g.in(grad_coeffs, g.z.co), o_gj = g.in(grad_cost, (size_t)s.B * 8);
     const size_t o_gw = g.out(grad_waypoints, g.z.wp), o_gt = g.out(grad_times, g.z.tm), o_gb = g.out(grad_bc, g.z.bc);
     const size_t o_st = g.out(status, (size_t)s.B * 4), o_ws = g.hc.scratch(n_ws);
     return g.run([&] {
-        return dispatch_cost_vjp(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(g.bc), g.ptr(o_gc), g.ptr<const double>(o_gj), g.ptr(o_gw),
-                                 g.ptr(o_gt), g.ptr(o_gb), g.ptr<int32_t>(o_st), g.ptr<const int64_t>(g.seg_off),
-                                 g.ptr<const double>(g.vw_per), g.ptr(o_ws), n_ws, st);
+        return dispatch_vjp(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(g.bc), g.ptr(o_gc), g.ptr<const double>(o_gj), g.ptr(o_gw),
+                            g.ptr(o_gt), g.ptr(o_gb), g.ptr<int32_t>(o_st), g.ptr<const int64_t>(g.seg_off),
+                            g.ptr<const double>(g.vw_per), g.ptr(o_ws), n_ws, st);
     });
 }
 

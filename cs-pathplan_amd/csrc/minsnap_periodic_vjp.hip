@@ -21,7 +21,7 @@
 // One lane per trajectory, no cross-lane operation, no atomics, every sum in a fixed order: two calls give identical
 // bits, and a lane's arithmetic never depends on its neighbours.  Every loop runs over the segments only.
 //
-// load_rec / dbar_axis / powers repeat minsnap_vjp.hip's helpers of the same names (file-local there).
+// load_rec / dbar_axis / powers repeat the helpers of the same names in minsnap_vjp_device.h.
 #include "minsnap_device.h"
 #include "minsnap_periodic_vjp.h"
 

@@ -1,6 +1,6 @@
-// minsnap_vjp_device.h -- device helpers shared by the reverse-mode kernels of the open-chain solve (minsnap_vjp.hip,
-// minsnap_cost_vjp.hip): record loads, d_bar = M(T)^-T p_bar, powers of T and the in-wave sum.  All forced inline, so a
-// kernel that includes them compiles to what it would with the text in its own file.
+// minsnap_vjp_device.h -- device helpers of the open-chain solve's reverse-mode kernel (minsnap_vjp.hip): record loads,
+// d_bar = M(T)^-T p_bar, powers of T and the in-wave sum.  All forced inline, so a kernel that includes them compiles to
+// what it would with the text in its own file.
 #pragma once
 #include "minsnap_device.h"
 

@@ -236,6 +236,13 @@ def test_combined_is_vjp_plus_cost_only(csp, order):
         errs.append(rel_err_rows(both[2].reshape(-1 if per_bc else 1, 12), ref[2].reshape(-1 if per_bc else 1, 12)))
         print("order %d per_bc=%d: combined vs VJP + cost-only %.2e" % (order, per_bc, max(errs)))
         assert max(errs) < GATE_NUMPY[order], errs
+        # grad_cost = 0: the J_bar instantiation of the kernel against the one compiled without the J_bar terms
+        zero = _run(csp, order, wp, tm, bc, w, pbar, np.zeros_like(jbar))
+        plain = [_host(a) for a in (v.waypoints, v.times, v.bc)]
+        errs0 = [rel_err_rows(a.reshape(B, -1), b.reshape(B, -1)) for a, b in zip(zero[:2], plain[:2])]
+        errs0.append(rel_err_rows(zero[2].reshape(-1 if per_bc else 1, 12), plain[2].reshape(-1 if per_bc else 1, 12)))
+        print("order %d per_bc=%d: combined with grad_cost = 0 vs VJP %.2e" % (order, per_bc, max(errs0)))
+        assert max(errs0) < GATE_NUMPY[order], errs0
 
 
 @pytest.mark.parametrize("order", ORDERS)

@@ -1,10 +1,10 @@
 """Reverse-mode kernel (csp_minsnap_solve_batch_vjp) against the generic forward kernel in the same run.
 
-    python tools/vjp_bench.py [--steps K] [--warmup W]          (on the GPU box; prints one JSON line)
+    python tools/vjp_bench.py [--steps K] [--warmup W] [--order O]     (on the GPU box; prints one JSON line)
 
-Shapes: C3 (B = 65536, S = 16, order 4, fp64, shared bc, all three gradients) and a ragged batch with S ~ U{4..64} at
-order 4.  Algorithmic bytes per trajectory: p_bar read (3 S 2o words) + waypoints and times read + their gradients
-written, 8 bytes a word -- 4144 B at C3.  The forward is solve_batch(force_generic=True) on the same inputs."""
+Shapes: C3 (B = 65536, S = 16, fp64, shared bc, all three gradients) and a ragged batch with S ~ U{4..64}, both at order O
+(default 4).  Algorithmic bytes per trajectory: p_bar read (3 S 2o words) + waypoints and times read + their gradients
+written, 8 bytes a word -- 4144 B at C3, order 4.  The forward is solve_batch(force_generic=True) on the same inputs."""
 import argparse
 import ctypes
 import importlib
@@ -65,14 +65,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--order", type=int, default=4, choices=(2, 3, 4, 5))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
-    o = 4
+    o = a.order
     B, S = 65536, 16
     wp, tm = synth.make_batch(B, S, config_id=3)
     bc = torch.from_numpy(np.random.default_rng(0).normal(size=(1, 4, 3))).to(dev)
     out = [measure(dev, torch.from_numpy(wp).to(dev), torch.from_numpy(tm).to(dev), bc, o, a.steps, a.warmup,
-                   label="C3: B=65536 x 16 segments, order 4, fp64, shared bc, all gradients")]
+                   label="C3: B=65536 x 16 segments, order %d, fp64, shared bc, all gradients" % o)]
     Br = 16384
     rng = np.random.default_rng(5)
     lens = rng.integers(4, 65, size=Br)
@@ -84,7 +85,7 @@ def main():
         wp_r[off[b] + b:off[b + 1] + b + 1] = np.concatenate([p0, p0 + np.cumsum(rng.normal(size=(lens[b], 3)), axis=0)])
         tm_r[off[b]:off[b + 1]] = rng.uniform(0.5, 2.0, size=lens[b])
     out.append(measure(dev, torch.from_numpy(wp_r).to(dev), torch.from_numpy(tm_r).to(dev), bc, o, a.steps, a.warmup,
-                       seg_offsets=torch.from_numpy(off).to(dev), label="ragged: B=16384, S ~ U{4..64}, order 4, fp64, shared bc"))
+                       seg_offsets=torch.from_numpy(off).to(dev), label="ragged: B=16384, S ~ U{4..64}, order %d, fp64, shared bc" % o))
     print(json.dumps({"tool": "vjp_bench", "results": out}))
 
 
