@@ -17,9 +17,9 @@
 // (O=4, S=16: 536 + 3072 = 3608 B); no workspace.
 #pragma once
 #include "minsnap_device.h"
+#include "minsnap_fixed_plan.h"
 #include "minsnap_launch.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 #ifdef CSP_STAMPS
@@ -53,13 +53,10 @@ namespace fixedk {
 // slice's LDS-DMA in flight across its barriers.
 // 16-byte coefficient store.  NT: non-temporal, for batches whose coefficients exceed the Infinity Cache -- B = 524288:
 // 348 us against 378 us (67.9 % against 62.5 % of HBM peak); at B = 65536, whose 201 MB the cache absorbs, the ordinary
-// store is the faster one (42.5 us against 46.1 us), so the launcher decides (nt_stores_for) and picks the instantiation.
-// The flavour is a template parameter: as a run-time select every store was a pair of branches around both flavours,
+// store is the faster one (42.5 us against 46.1 us), so the launcher decides (plan_fixed, minsnap_fixed_plan.h) and picks the
+// instantiation.  The flavour is a template parameter: as a run-time select every store was a pair of branches around both flavours,
 // which cut the bursts into two-instruction basic blocks.
 typedef double v2d_t __attribute__((ext_vector_type(2)));
-// Store policy of a full-slice kernel's coefficient stores, a compile-time property of the instantiation: ordinary,
-// non-temporal, or (values >= 16) write-through with that value as the buffer store's cache bits.
-constexpr int SP_PLAIN = 0, SP_NT = 1, SP_WT = 16;
 template <bool NT> __device__ __forceinline__ void store16(char *p, const double2 &v) {
     if constexpr (NT) {
         v2d_t x = {v.x, v.y};
@@ -240,7 +237,7 @@ __device__ __forceinline__ void recover(double Ps, double dP, const double (&xs)
 // arithmetic once the segment loop is unrolled.
 template <int O, int S> struct LineGeom {
     static constexpr int RECB = 48 * O;                       // bytes per (trajectory, segment) record
-    static constexpr bool OK = (S * RECB) % 128 == 0;
+    static constexpr bool OK = starts_on_lines(O, S);
     // bytes waiting for their line are a multiple of gcd(RECB, 128) below 128: 96 / 112 / 64 / 112 at orders 2 / 3 / 4 / 5
     static constexpr int GCD = RECB % 128 == 0 ? 128 : (RECB % 64 == 0 ? 64 : (RECB % 32 == 0 ? 32 : 16));
     static constexpr int RINGB = ((RECB + 128 - GCD + 127) / 128) * 128;
@@ -927,67 +924,18 @@ __global__ void __launch_bounds__(128) minsnap_fixed_persistent_wt_kernel(Generi
 hipError_t launch_persistent_wt_o4(const GenericArgs &f, int n_slices, unsigned grid, hipStream_t st);   // minsnap_fixed_o4d.hip
 
 // ---- host side: launch one order's kernels -----------------------------------------------------
-// Trajectories per workgroup for the one-workgroup-per-slice kernel.  A small batch is latency-bound -- a lone wave's
-// instruction stream is the run time -- so what helps is fewer instructions per lane, not more workgroups: with the
-// three-lanes-per-trajectory mapping (order 4) batches of B <= 32 * CUs trajectories run as
-// slices of 16 (measured, B = 4096, S = 8: 8.2 us one lane per trajectory in slices of 64, 7.9 us in slices of 16,
-// 6.1 us with three lanes per trajectory; B = 8192: 9.3 -> 8.8 us).  Everything else keeps 64.  CSP_SLICE_W overrides
-// (tuning experiments: 8, 16, 32, 64).
-inline int narrow_slice(int64_t B, int cus, bool axis_lanes) {
-    static const int forced = [] { const char *e = std::getenv("CSP_SLICE_W"); return e ? std::atoi(e) : 0; }();
-    if (forced == 8 || forced == 16 || forced == 32 || forced == 64) return forced;   // even: 16-byte pieces stay aligned
-    return (axis_lanes && B <= 32 * (int64_t)cus) ? 16 : 64;
-}
-inline bool axis_lanes_enabled() {   // CSP_AXIS_LANES=0 switches the three-lanes-per-trajectory mapping off (A/B runs)
-    static const bool on = [] { const char *e = std::getenv("CSP_AXIS_LANES"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
-// Non-temporal coefficient stores (store16) once the coefficients of the launch exceed the 256 MB Infinity Cache;
-// CSP_NT_STORES=0 / 1 forces the choice (A/B runs).
-inline int nt_forced() {
-    static const int forced = [] { const char *e = std::getenv("CSP_NT_STORES"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-    return forced;
-}
-inline int nt_stores_for(int64_t B, int S, int O) {
-    const int forced = nt_forced();
-    if (forced >= 0) return forced;
-    return (double)B * S * 6 * O * 8.0 > 256.0 * 1024 * 1024 ? 1 : 0;
-}
-
-// Store policy of a launch's whole slices (SP_PLAIN / SP_NT / SP_WT), from the bytes of coefficients it writes.
-// Write-through exists for the paired order-4 records only (wt_shape: even S >= 4; default layout, persistent kernel), and
-// launch_s asks this rule for those shapes alone: every other shape keeps nt_stores_for.  CSP_STORE_POLICY=plain|nt|wt
-// forces the choice for them (A/B runs) and takes precedence over CSP_NT_STORES; a forced `wt` that meets the
-// one-workgroup-per-slice kernel (CSP_FLAG_NO_PERSISTENT, per-trajectory boundary conditions) stores ordinarily.  Up to the
-// chip's aggregate L2 (8 x 4 MiB) the stores stay ordinary whatever the sweep says: a following kernel
-// (the sampler after a plan) still finds those lines in L2.  Above the Infinity Cache: non-temporal, as before.
-constexpr double WT_ABOVE_BYTES = 32.0 * 1024 * 1024, WT_UP_TO_BYTES = 256.0 * 1024 * 1024;
-inline int store_policy_forced() {
-    static const int forced = [] {
-        const char *e = std::getenv("CSP_STORE_POLICY");
-        if (!e) return -1;
-        return e[0] == 'w' ? SP_WT : (e[0] == 'n' ? SP_NT : SP_PLAIN);
-    }();
-    return forced;
-}
-constexpr bool wt_shape(int S, int O) { return O == 4 && S >= 4 && S % 2 == 0; }
-inline int store_policy_for(double bytes, int S, int O) {
-    const int forced = store_policy_forced();
-    if (forced >= 0) return forced;
-    if (nt_forced() >= 0) return nt_forced() ? SP_NT : SP_PLAIN;
-    if (bytes > WT_ABOVE_BYTES && bytes <= WT_UP_TO_BYTES && wt_shape(S, O)) return SP_WT;
-    return bytes > WT_UP_TO_BYTES ? SP_NT : SP_PLAIN;
-}
-
+// Which variant runs is decided by plan_fixed (minsnap_fixed_plan.h); this only executes its plan.
 template <int O, int S, bool SEGMAJ_OK>
 hipError_t launch_s(const GenericArgs &a, int cus, hipStream_t st) {
+    static_assert(SEGMAJ_OK == seg_major_order(O), "the plan refuses segment-major output exactly where it is not instantiated");
+    const FixedPlan p = plan_fixed({O, S, a.B, cus, a.seg_major != 0, a.persistent != 0, a.bc_per_traj != 0, a.vw_per != nullptr, a.multi != nullptr},
+                                   fixed_env());
     const dim3 block(128);
-    if (a.multi) {
-        // csp_minsnap_solve_multi: every batch cut into slices of 64 (one lane per trajectory), one workgroup per slice,
-        // all of them in one grid
+    if (p.path == FP_REFUSED) return hipErrorInvalidValue;
+    if (p.path == FP_MULTI) {
+        // csp_minsnap_solve_multi: one lane per trajectory, the grid is the table's
         GenericArgs t = a;
-        t.slice_w = 64;
+        t.slice_w = p.slice_w;
         t.multi = nullptr;
         const dim3 grid((unsigned)a.multi->first_slice[a.multi->n]);
         bool any_status = false;
@@ -996,15 +944,12 @@ hipError_t launch_s(const GenericArgs &a, int cus, hipStream_t st) {
         else hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, false, false, false>), grid, block, 0, st, t, *a.multi);
         return hipGetLastError();
     }
-    const bool axis_ok = O == 4 && !a.seg_major && axis_lanes_enabled();
-    const int w = narrow_slice(a.B, cus, axis_ok);
-    if (w < 64 && !a.seg_major) {
+    if (p.path == FP_NARROW) {
         GenericArgs t = a;
-        t.slice_w = w;
-        const dim3 grid((unsigned)((a.B + w - 1) / w));
+        t.slice_w = p.slice_w;
+        const dim3 grid((unsigned)p.grid);
         if constexpr (O == 4) {
-            // slices of <= 16 trajectories: three lanes per trajectory, one per axis (fixed_body NAX = 1)
-            if (w <= 16 && axis_ok) {
+            if (p.axis_lanes) {
                 if (a.status) hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, true, false, false, 1>), grid, block, 0, st, t, MultiTable{});
                 else hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, false, false, false, 1>), grid, block, 0, st, t, MultiTable{});
                 return hipGetLastError();
@@ -1014,12 +959,10 @@ hipError_t launch_s(const GenericArgs &a, int cus, hipStream_t st) {
         else hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, false, false, false>), grid, block, 0, st, t, MultiTable{});
         return hipGetLastError();
     }
-    const int64_t n_full = a.B / 64, rem = a.B % 64;
-    const int64_t pgrid = n_full < 2 * (int64_t)cus ? n_full : 2 * (int64_t)cus;  // two workgroups per CU
     GenericArgs t = a;  // tail: the last B % 64 trajectories, one workgroup
-    if (rem) {
-        const int64_t off = n_full * 64;
-        t.B = rem;
+    if (p.rem) {
+        const int64_t off = p.n_full * 64;
+        t.B = p.rem;
         t.wp = (const double *)a.wp + off * (a.S + 1) * 3;
         t.times = (const double *)a.times + off * a.S;
         if (a.seg_major) t.Boffset = off;   // segment-major records are addressed from the batch start
@@ -1028,46 +971,33 @@ hipError_t launch_s(const GenericArgs &a, int cus, hipStream_t st) {
         if (a.status) t.status = a.status + off;
         if (a.vw_per) t.vw_per = a.vw_per + off;
     }
+    GenericArgs f = a;  // the whole slices
+    f.B = p.n_full * 64;
+    f.nt_stores = p.store == SP_NT;
     auto go = [&](auto status_tag, auto segmaj_tag) {
         constexpr bool ST = decltype(status_tag)::value, SM = decltype(segmaj_tag)::value;
-        if (n_full) {
-            GenericArgs f = a;
-            f.B = n_full * 64;
-            // Non-temporal stores need lines that leave whole: order 4 (paired 192-byte records) and, from round 3 on, every
-            // order whose trajectories start on 128-byte lines (LineRing).  Record-at-a-time stores of 96- / 144- / 240-byte
-            // records share lines between instructions, which the L2 merges for ordinary stores and not for non-temporal
-            // ones (round 2, B = 524288: 261 / 392 / 312 us ordinary against 499 / 841 / 404 us non-temporal).
-            constexpr bool WHOLE_LINES = !SM && (O == 4 || LineGeom<O, S>::OK);
-            f.nt_stores = (WHOLE_LINES || O == 4) ? nt_stores_for(a.B, S, O) : (nt_forced() == 1 ? 1 : 0);
-            bool wt = false;
-            if constexpr (wt_shape(S, O) && !SM) {
-                const int sp = store_policy_for((double)a.B * S * 6 * O * 8.0, S, O);
-                wt = sp == SP_WT && a.persistent && !a.bc_per_traj && !a.vw_per;
-                if (store_policy_forced() >= 0) f.nt_stores = sp == SP_NT;
-            }
-            // the store flavour is a compile-time property of the kernel: one instantiation each
-            auto full = [&](auto nt_tag) {
-                constexpr bool NT = decltype(nt_tag)::value;
-                if (a.persistent && !a.bc_per_traj && !a.vw_per) hipLaunchKernelGGL((minsnap_fixed_persistent_kernel<O, S, ST, SM, NT>), dim3((unsigned)pgrid), block, 0, st, f, (int)n_full);
-                else hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, ST, true, SM, 3, NT>), dim3((unsigned)n_full), block, 0, st, f, MultiTable{});
-            };
-            if (wt) (void)launch_persistent_wt_o4(f, (int)n_full, (unsigned)pgrid, st);
-            else if (f.nt_stores) full(std::true_type{});
+        // the store flavour is a compile-time property of the kernel: one instantiation each
+        auto full = [&](auto nt_tag) {
+            constexpr bool NT = decltype(nt_tag)::value;
+            if (p.body == FB_PERSISTENT) hipLaunchKernelGGL((minsnap_fixed_persistent_kernel<O, S, ST, SM, NT>), dim3((unsigned)p.grid), block, 0, st, f, (int)p.n_full);
+            else hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, ST, true, SM, 3, NT>), dim3((unsigned)p.grid), block, 0, st, f, MultiTable{});
+        };
+        if (p.n_full) {
+            if (p.body == FB_PERSISTENT_WT) (void)launch_persistent_wt_o4(f, (int)p.n_full, (unsigned)p.grid, st);
+            else if (p.store == SP_NT) full(std::true_type{});
             else full(std::false_type{});
         }
-        if (rem) hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, ST, false, SM>), dim3(1), block, 0, st, t, MultiTable{});
+        if (p.rem) hipLaunchKernelGGL((minsnap_fixed_kernel<O, S, ST, false, SM>), dim3(1), block, 0, st, t, MultiTable{});
     };
-    if (a.seg_major) {
-        if constexpr (SEGMAJ_OK) {
+    if constexpr (SEGMAJ_OK) {
+        if (a.seg_major) {
             if (a.status) go(std::true_type{}, std::true_type{});
             else go(std::false_type{}, std::true_type{});
-        } else {
-            return hipErrorInvalidValue;
+            return hipGetLastError();
         }
-    } else {
-        if (a.status) go(std::true_type{}, std::false_type{});
-        else go(std::false_type{}, std::false_type{});
     }
+    if (a.status) go(std::true_type{}, std::false_type{});
+    else go(std::false_type{}, std::false_type{});
     return hipGetLastError();
 }
 

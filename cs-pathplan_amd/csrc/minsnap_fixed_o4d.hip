@@ -1,7 +1,7 @@
 // minsnap_fixed_o4d.hip -- instantiates the write-through flavour of the persistent order-4 kernel
 // (minsnap_fixed_impl.h: minsnap_fixed_persistent_wt_kernel) for the even segment counts, whose records leave as
 // paired whole-line bursts.  launch_s (minsnap_fixed_o4a/b/c.hip) calls it for launches whose coefficients exceed the
-// chip's aggregate L2 (store_policy_for).
+// chip's aggregate L2 and fit the Infinity Cache (plan_fixed in minsnap_fixed_plan.h).
 #include "minsnap_fixed_impl.h"
 
 #ifdef CSP_STAMPS

@@ -75,16 +75,14 @@ template <int O, bool PEN> __device__ __forceinline__ double q_ee(const PSeg<O> 
     return PEN ? __builtin_fma(pw * s.h[O + r + 1], s.h[O + c + 1], q) : q;
 }
 
-// Dense residency (order 2, S >= 8): under 40 KB of LDS and 256 registers, so that FOUR workgroups share a CU.
-template <int O, int S> constexpr bool path_dense = (O == 2 && S >= 8);
-// doubles per staging row: the dense variant gives up the two padding doubles (2-way conflicts on its six
+// doubles per staging row: the dense variant (path_dense, minsnap_fixed_plan.h) gives up the two padding doubles (2-way conflicts on its six
 // ds_write_b128 per segment, a few dozen clocks) for 2 KB of LDS
-template <int O, int S> constexpr int path_stage_row = path_dense<O, S> ? FixedLds<O, S>::REC : FixedLds<O, S>::STAGE_ROW;
+template <int O, int S> constexpr int path_stage_row = path_dense(O, S) ? FixedLds<O, S>::REC : FixedLds<O, S>::STAGE_ROW;
 // Dense residency WITH whole-line stores (round 3; order 2, S = 8, 12, 16 -- trajectories that start on lines): a
 // 64-row ring tile does not fit under 40 KB, so the tile has 32 rows and a segment's records leave in two half-wave
 // phases (HalfRing below); the bytes a phase would have to keep in the tile for the next record are kept in REGISTERS
 // instead (they are part of the previous record, which the lane still holds) and re-written with it.
-template <int O, int S> constexpr bool path_dense_ring = path_dense<O, S> && LineGeom<O, S>::OK;
+template <int O, int S> constexpr bool path_dense_ring = path_dense(O, S) && LineGeom<O, S>::OK;
 template <int O, int S> constexpr int path_tile_doubles = path_dense_ring<O, S> ? 32 * 26 : 64 * path_stage_row<O, S>;
 
 // Half-height ring of the dense order-2 kernel: rows of 192 ring bytes (+ 16 bytes of padding: the stride in dwords is an
@@ -325,7 +323,7 @@ __device__ __forceinline__ void path_sweep(const GenericArgs &a, int64_t b0, int
     const unsigned g_off = (unsigned)(grp * RS + lane_in * 16);
     // whole-line stores through the ring of minsnap_fixed_impl.h (LineRing) wherever the trajectories start on 128-byte
     // lines; the dense order-2 variant keeps its 96-byte tile rows (no room for a ring under 40 KB of LDS)
-    constexpr bool RING = PEN && LineGeom<O, S>::OK && !path_dense<O, S>;
+    constexpr bool RING = PEN && LineGeom<O, S>::OK && !path_dense(O, S);
     constexpr bool DRING = PEN && path_dense_ring<O, S>;   // order 2 only: half-height ring, records held in registers
     using LR = LineRing<O, S, BOTTOM>;
     double cprev[DRING ? 12 : 1] = {};
@@ -516,7 +514,7 @@ __device__ __forceinline__ void path_sweep(const GenericArgs &a, int64_t b0, int
                 //    stored factors filling most of the file, end in scratch (1.4 KB/lane at order 4, S = 16: 170 us
                 //    instead of 98).
                 double ratio = 0.0;
-                if constexpr (O == 2 && !path_dense<O, S>) {
+                if constexpr (O == 2 && !path_dense(O, S)) {
                     ratio = (len2 > 1e-12) ? d2 * fast_rcp(len2) : 0.0;
                 } else {
                     if (len2 > 1e-12) {
@@ -611,7 +609,7 @@ __device__ __forceinline__ void path_role(const GenericArgs &a, int64_t b0, int 
 // One workgroup per 64-trajectory slice (path-penalty solves are not the streaming headline: no
 // persistent/prefetch structure here).  `skip` marks trajectories the re-solve loop has finished.
 template <int O, int S, bool STATUS, bool NT>
-__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(path_dense<O, S> ? 2 : 1)))
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(path_dense(O, S) ? 2 : 1)))
 minsnap_fixed_path_kernel(GenericArgs a) {
     using L = FixedLds<O, S>;
     constexpr int M = 2 * O;
@@ -619,7 +617,7 @@ minsnap_fixed_path_kernel(GenericArgs a) {
     // times in registers) and lose their padding, which brings the workgroup under 40 KB of LDS: four workgroups per
     // CU = two waves per SIMD (the order-2 sweep fits 256 registers once its segments are separate basic blocks),
     // and the 1024 workgroups of a 65536-trajectory batch are resident at once.
-    constexpr bool DENSE = path_dense<O, S>;
+    constexpr bool DENSE = path_dense(O, S);
     constexpr int TILE = path_tile_doubles<O, S>;
     static_assert(L::CARRY * 64 <= TILE, "carries must fit in a staging tile");
     static_assert(!DENSE || 64 * S <= 2 * TILE, "the image of the times must fit under the staging tiles");
@@ -712,38 +710,20 @@ minsnap_fixed_path_kernel(GenericArgs a) {
     else path_role<O, S, true, STATUS, DENSE, NT>(a, b0, rows, b, lane, l_wp, l_tm, l_hw, l_stage + TILE, l_stage + TILE, l_stage, l_skip, l_dev, l_bits);
 }
 
+// Grid, store flavour and stagger come from plan_fixed_path (minsnap_fixed_plan.h).
 template <int O, int S> hipError_t launch_path_s(const GenericArgs &a, hipStream_t st) {
-    const dim3 grid((unsigned)((a.B + 63) / 64)), block(128);
+    const PathPlan p = plan_fixed_path(O, S, a.B, fixed_env());
+    const dim3 grid((unsigned)p.grid), block(128);
     GenericArgs f = a;
-    // Non-temporal coefficient stores (store16) at order 4 from 48 MB of coefficients on (CSP_NT_STORES=0 / 1 forces the
-    // choice for A/B runs).  Measured at S = 16 (tools/path_nt_ab.py; three boxes): B = 16384 / 32768 / 65536 / 98304 / 131072 /
-    // 262144 / 524288: 40.7 / 45.1 / 93-95 / 145 / 188 / 368 / 723 us against 44.1 / 49.3 / 95.5-97.6 / 163 / 214 / 419 /
-    // 817 us with ordinary stores, and WRITE_SIZE 1.013x the coefficients instead of 1.083x: unlike the unpenalised
-    // kernel (section 5.1: ordinary stores win while the coefficients fit the Infinity Cache) this one computes for most
-    // of its time and gains from lines that leave whole.  Orders 2 and 3 LOSE at every size (B = 524288: 503 against
-    // 306 us, 876 against 620 us): their 96- and 144-byte records leave 128-byte lines shared between store
-    // instructions, and a non-temporal partial line is not merged on the way out.
-    // Launches that write less than 48 MB keep ordinary stores: nothing measurable to gain (B = 8192: 40.2 against
-    // 40.6 us; one order-4 flight through the host C-ABI: 1167-1186 us either way), and the reader that follows a small
-    // solve (the sampler) then finds the coefficients in the cache.
-    const bool big = (double)a.B * S * 6 * O * 8.0 >= 48.0 * 1024 * 1024;
-    // Round 3: orders 2 / 3 store whole lines too (LineRing) where the trajectories start on lines -- except the dense
-    // order-2 variant -- and take the same rule.
-    constexpr bool WHOLE_LINES = O == 4 || LineGeom<O, S>::OK;   // incl. the dense order-2 variant (HalfRing)
-    f.nt_stores = nt_forced() >= 0 ? nt_forced() : (WHOLE_LINES && big ? 1 : 0);
-    static const int stagger_env = [] { const char *e = std::getenv("CSP_PATH_STAGGER"); return e ? std::atoi(e) : -1; }();
-    // measured at B = 65536, S = 16 (tools/path_bench.py, CSP_PATH_STAGGER = 0 / 1 / 2 / 3 / 4 / 6): order 3 58.4 / 57.3 / 57.7 /
-    // 61.0 / 65.5 / 76.7 us, order 4 86.4 / 85.0 / 86.8 / 84.0 / 86.2 / 95.7 us -- a 2-3 % effect; scaled with the sweep length
-    // (dense order-2 variant: the four workgroups of a CU start stagger x S x 64 clocks apart; with the closed-form search of
-    // round 3 -- CSP_PATH_STAGGER = 0 / 2 / 3 / 4 / 5 / 6 / 8: 33.2 / 30.6 / 30.2 / 30.3 / 30.3 / 30.8 / 32.1 us at B = 65536, S = 16)
-    f.stagger = stagger_env >= 0 ? stagger_env : (path_dense<O, S> ? 4 : O == 3 ? (S + 8) / 16 : O == 4 ? (3 * S + 8) / 16 : 0);
+    f.nt_stores = p.nt;
+    f.stagger = p.stagger;
     // the store flavour is a compile-time property of the kernel (store16): one instantiation each
     auto go = [&](auto nt_tag) {
         constexpr bool NT = decltype(nt_tag)::value;
         if (a.status) hipLaunchKernelGGL((minsnap_fixed_path_kernel<O, S, true, NT>), grid, block, 0, st, f);
         else hipLaunchKernelGGL((minsnap_fixed_path_kernel<O, S, false, NT>), grid, block, 0, st, f);
     };
-    if (f.nt_stores) go(std::true_type{});
+    if (p.nt) go(std::true_type{});
     else go(std::false_type{});
     return hipGetLastError();
 }

@@ -47,7 +47,7 @@ struct GenericArgs {
     const int32_t *skip;    // generic kernel: [B] non-zero = leave this trajectory untouched (or null)
     int tau_mode;           // path kernel: 0 find t* each call; 1 find and store in tstar; 2 reuse tstar (re-solve loop)
     int slice_w = 64;       // fixed kernels, one-workgroup-per-slice variant: trajectories per workgroup (small batches
-                            // are cut into narrower slices so that every CU gets one, see fixedk::narrow_slice)
+                            // are cut into narrower slices, see fixedk::plan_fixed in minsnap_fixed_plan.h)
     int nt_stores = 0;      // fixed kernels, whole slices: non-temporal coefficient stores -- set by the launcher for
                             // batches whose coefficients exceed the Infinity Cache (picks the kernels' NT instantiation, fixedk::store16)
     int stagger = 0;        // path kernels (orders 3-4): start delay of a CU's second workgroup, units of 8128 clocks
