@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "csp_minsnap_timeopt_workspace_bytes",
     "csp_minsnap_solve_periodic_batch", "csp_minsnap_periodic_workspace_bytes",
     "csp_minsnap_solve_periodic_batch_vjp", "csp_minsnap_periodic_vjp_workspace_bytes",
+    "csp_minsnap_eval_batch", "csp_minsnap_eval_batch_vjp",
     "csp_minsnap_solve_mixed", "csp_minsnap_mixed_workspace_bytes", "csp_minsnap_solve_multi",
     "csp_minsnap_plan_batch", "csp_minsnap_plan_workspace_bytes", "csp_minsnap_sample_batch",
     "csp_minsnap_generate_batch", "csp_minsnap_sample_capacity",
@@ -136,6 +137,8 @@ _PROTOTYPES = {
     "csp_minsnap_periodic_workspace_bytes": (_SZ, [_D]),
     "csp_minsnap_solve_periodic_batch_vjp": (_I, [_D] + [_P] * 8 + [_SZ, _P]),
     "csp_minsnap_periodic_vjp_workspace_bytes": (_SZ, [_D]),
+    "csp_minsnap_eval_batch": (_I, [_D, _P, _P, _P, _I64, _I32, _P, _P, _P, _P]),
+    "csp_minsnap_eval_batch_vjp": (_I, [_D, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     "csp_minsnap_solve_multi": (_I, [_D, _I] + [_P] * 7),
     "csp_minsnap_solve_mixed": (_I, [_D] + [_P] * 8 + [_SZ, _P]),
     "csp_minsnap_mixed_workspace_bytes": (_SZ, [_D]),
@@ -1094,6 +1097,137 @@ def sample_batch(times, coeffs, sample_distance, capacity, order=None, out=None,
     _check(_lib.csp_minsnap_sample_batch(ctypes.byref(desc), mem.ptr(times), mem.ptr(coeffs), float(sample_distance),
                                          int(capacity), mem.ptr(samples), mem.ptr(counts), mem.ptr(stats), mem.stream()))
     return samples, counts, stats
+
+
+class EvalResult:
+    """eval_batch: values [B,Q,D,3], seg_index [B,Q] i32 (or None), status [B] i32 (or None)."""
+    __slots__ = ("values", "seg_index", "status")
+
+    def __init__(self, values, seg_index, status):
+        self.values, self.seg_index, self.status = values, seg_index, status
+
+
+class EvalVjpResult:
+    """Gradients of eval_batch_vjp; a gradient that was not asked for is None."""
+    __slots__ = ("coeffs", "times", "query", "status")
+
+    def __init__(self, coeffs, times, query, status):
+        self.coeffs, self.times, self.query, self.status = coeffs, times, query, status
+
+
+_EVAL_VJP_WANT = ("coeffs", "times", "query")
+
+
+class _EvalInputs:
+    """times / coeffs / query of one evaluation call, contiguous in the memory space of `times`, and their descriptor."""
+
+    def __init__(self, times, coeffs, query, order, seg_offsets, max_segments):
+        self.mem = mem = _mem(times)
+        self.io = io = mem.kind(times)
+        self.times, self.coeffs, self.query = mem.contig(times, io), mem.contig(coeffs, io), mem.contig(query, io)
+        self.seg_offsets, self.B, self.S, self.total, smax = _ragged_dims(mem, seg_offsets, self.times, max_segments)
+        self.order = int(order) if order is not None else int(self.coeffs.shape[-1]) // 2
+        if math.prod(self.coeffs.shape) != self.total * 6 * self.order:
+            raise ValueError("coeffs must hold %d elements ([segments,3,2*order])" % (self.total * 6 * self.order))
+        if self.query.ndim != 2 or self.query.shape[0] != self.B:
+            raise ValueError("query must be [B,Q] with B = %d" % self.B)
+        self.Q = int(self.query.shape[1])
+        if mem.mem_space == MEM_DEVICE and self.coeffs.data_ptr() % 16:   # records are read in 16-byte pieces
+            self.coeffs = self.coeffs.clone()
+        self.desc = make_desc(self.order, self.B, self.S, _dtype_code(io), mem_space=mem.mem_space,
+                              seg_offsets_ptr=mem.ptr(self.seg_offsets), max_segments=(smax or 0) if self.seg_offsets is not None else 0,
+                              device_id=mem.device_id)
+
+
+def eval_batch(times, coeffs, query, num_derivs=3, order=None, seg_offsets=None, max_segments=None, want_seg_index=False,
+               want_status=False, stream=None):
+    """Position and its first num_derivs - 1 derivatives of every trajectory at its query times
+    (csp_minsnap_eval_batch).  times [B,S], coeffs [B,S,3,2o] as solve_batch or
+    solve_periodic_batch return them, query [B,Q] global times from the trajectory's start (clamped to [0, sum T]; a
+    query on a knot belongs to the later segment).  Ragged: times [sum S_b], coeffs [sum S_b,3,2o], seg_offsets [B+1].
+    numpy arrays -> host memory (synchronous), torch CUDA tensors -> device memory (asynchronous on the current stream).
+    Returns EvalResult(values [B,Q,D,3], seg_index, status)."""
+    ei = _EvalInputs(times, coeffs, query, order, seg_offsets, max_segments)
+    mem, p, D = ei.mem, ei.mem.ptr, int(num_derivs)
+    out = mem.empty((ei.B, ei.Q, max(D, 0), 3), ei.io)
+    sg = mem.empty((ei.B, ei.Q), "i32") if want_seg_index else None
+    stt = mem.zeros((ei.B,), "i32") if want_status else None   # zeros: no query, no launch
+    _check(_lib.csp_minsnap_eval_batch(ctypes.byref(ei.desc), p(ei.times), p(ei.coeffs), p(ei.query), ei.Q, D, p(out), p(sg),
+                                       p(stt), mem.stream(stream)))
+    return EvalResult(out, sg, stt)
+
+
+def eval_batch_vjp(times, coeffs, query, grad_out, num_derivs=None, order=None, seg_offsets=None, max_segments=None,
+                   want=_EVAL_VJP_WANT, want_status=False, stream=None):
+    """Vector-Jacobian product of eval_batch (csp_minsnap_eval_batch_vjp): given grad_out = dL/dvalues [B,Q,D,3] (D is
+    taken from it unless num_derivs is given), returns EvalVjpResult(dL/dcoeffs, dL/dtimes, dL/dquery, status) for the
+    names in `want`.  dL/dtimes is the explicit dependence through the local time only; the dependence of the
+    coefficients on the times is solve_batch_vjp's.  Every record of dL/dcoeffs is written.  Deterministic run to run."""
+    want = tuple(want)
+    for w in want:
+        if w not in _EVAL_VJP_WANT:
+            raise ValueError("want: a subset of %r" % (_EVAL_VJP_WANT,))
+    ei = _EvalInputs(times, coeffs, query, order, seg_offsets, max_segments)
+    mem, p = ei.mem, ei.mem.ptr
+    go = mem.contig(grad_out, ei.io)
+    D = int(num_derivs) if num_derivs is not None else int(go.shape[-2])
+    if math.prod(go.shape) != ei.B * ei.Q * D * 3:
+        raise ValueError("grad_out must hold %d elements ([B,Q,D,3])" % (ei.B * ei.Q * D * 3))
+    gco = mem.empty(ei.coeffs.shape, ei.io) if "coeffs" in want else None
+    gtm = mem.empty(ei.times.shape, ei.io) if "times" in want else None
+    gq = mem.empty(ei.query.shape, ei.io) if "query" in want else None
+    stt = mem.zeros((ei.B,), "i32") if want_status else None
+    _check(_lib.csp_minsnap_eval_batch_vjp(ctypes.byref(ei.desc), p(ei.times), p(ei.coeffs), p(ei.query), ei.Q, D, p(go), p(gco),
+                                           p(gtm), p(gq), p(stt), mem.stream(stream)))
+    return EvalVjpResult(gco, gtm, gq, stt)
+
+
+def _make_eval_autograd_fn():
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class EvalBatchFn(torch.autograd.Function):
+        """values = eval_batch(times, coeffs, query); backward = one eval_batch_vjp for the inputs that need it."""
+
+        @staticmethod
+        def forward(ctx, coeffs, times, query, num_derivs, seg_offsets, max_segments):
+            r = eval_batch(times.detach(), coeffs.detach(), query.detach(), num_derivs=num_derivs, seg_offsets=seg_offsets,
+                           max_segments=max_segments)
+            ctx.save_for_backward(coeffs, times, query, seg_offsets)
+            ctx.num_derivs, ctx.max_segments = num_derivs, max_segments
+            return r.values
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_values):
+            coeffs, times, query, seg_offsets = ctx.saved_tensors
+            needs = ctx.needs_input_grad[:3]
+            want = tuple(n for n, f in zip(_EVAL_VJP_WANT, needs) if f)
+            if not want:
+                return (None,) * 6
+            g = eval_batch_vjp(times, coeffs, query, grad_values, num_derivs=ctx.num_derivs, seg_offsets=seg_offsets,
+                               max_segments=ctx.max_segments, want=want)
+            gco = g.coeffs.reshape(coeffs.shape).to(coeffs.dtype) if needs[0] else None
+            gtm = g.times.to(times.dtype) if needs[1] else None
+            gq = g.query.to(query.dtype) if needs[2] else None
+            return gco, gtm, gq, None, None, None
+
+    return EvalBatchFn
+
+
+_eval_autograd_fn = None
+
+
+def eval_batch_autograd(coeffs, times, query, num_derivs=3, seg_offsets=None, max_segments=None):
+    """eval_batch as a differentiable torch op (CUDA tensors): returns the values [B,Q,D,3] -- bit-equal to
+    eval_batch(...).values -- with a grad_fn when coeffs, times or query require grad.  The backward pass is one
+    csp_minsnap_eval_batch_vjp for the inputs that need a gradient; first-order only (once_differentiable).  Chains with
+    solve_batch_autograd and solve_periodic_batch_autograd: pass their coefficients and the same times tensor, and
+    autograd adds this op's explicit time gradient to the solve's."""
+    global _eval_autograd_fn
+    if _eval_autograd_fn is None:
+        _eval_autograd_fn = _make_eval_autograd_fn()
+    return _eval_autograd_fn.apply(coeffs, times, query, num_derivs, seg_offsets, max_segments)
 
 
 def _geo(fn, pts, ref):

@@ -7,6 +7,7 @@
 // a set of optional outputs goes through ONE staging helper, Stage (with offsets_ok() and sizes_of()).
 #include "../../include/csp_minsnap.h"
 #include "minsnap_launch.h"
+#include "minsnap_eval.h"
 #include "minsnap_periodic_vjp.h"
 #include "minsnap_vjp.h"
 #include "minsnap_hoststage.h"
@@ -1704,6 +1705,113 @@ int csp_minsnap_solve_periodic_batch_vjp(const csp_minsnap_desc *desc, const voi
         return dispatch_periodic_vjp(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(o_gc), g.ptr<const double>(o_gj), g.ptr(o_gw),
                                      g.ptr(o_gt), g.ptr<int32_t>(o_st), g.ptr<const int64_t>(g.seg_off),
                                      g.ptr<const double>(g.vw_per), g.ptr(o_ws), st);
+    });
+}
+
+}  // extern "C"
+
+// ---- evaluation at arbitrary query times and its reverse mode (minsnap_eval.hip) ----
+namespace {
+
+// the two entries' limits on top of validate(): orders 2..5, trajectory-major coefficients, fp64 arithmetic, at most
+// 1024 segments per trajectory; 1 <= D <= 5 derivatives, Q >= 0 queries per trajectory
+int validate_eval(const csp_minsnap_desc *d, Shape &s, int64_t Q, int32_t D) {
+    int rc = validate(d, s);
+    if (rc != CSP_OK) return rc;
+    if (d->order < 2) return CSP_ERR_UNSUPPORTED;
+    if (d->flags & (CSP_FLAG_SEGMENT_MAJOR | CSP_FLAG_F32_ARITH)) return CSP_ERR_UNSUPPORTED;
+    if (s.Smax > csp::evalk::EVAL_MAX_SEGMENTS) return CSP_ERR_UNSUPPORTED;
+    if (D < 1 || D > csp::evalk::EVAL_MAX_DERIVS || Q < 0) return CSP_ERR_INVALID_ARG;
+    return CSP_OK;
+}
+
+csp::EvalArgs eval_args(const Shape &s, const void *tm, const void *co, const void *qr, int64_t Q, int32_t D,
+                        const int64_t *seg_off, int32_t *status) {
+    csp::EvalArgs a{};
+    a.times = tm; a.coeffs = co; a.query = qr; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.B = s.B; a.Q = Q; a.S = s.S; a.Smax = s.Smax; a.order = s.order; a.D = D;
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int csp_minsnap_eval_batch(const csp_minsnap_desc *desc, const void *times, const void *coeffs, const void *query,
+                           int64_t num_queries, int32_t num_derivs, void *out, int32_t *seg_index, int32_t *status,
+                           void *hip_stream) {
+    Shape s;
+    int rc = validate_eval(desc, s, num_queries, num_derivs);
+    if (rc != CSP_OK) return rc;
+    if (s.B == 0) return CSP_OK;
+    if (!times || !coeffs || (num_queries > 0 && (!query || !out))) return CSP_ERR_INVALID_ARG;
+    if (desc->mem_space == CSP_MEM_DEVICE) {
+        if ((uintptr_t)coeffs & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // records are read as 2-element vectors
+    } else if (!offsets_ok(desc, s)) {
+        return CSP_ERR_INVALID_ARG;
+    }
+    if (num_queries == 0) return CSP_OK;
+    rc = select_device(desc->device_id);
+    if (rc != CSP_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const auto launch = [&](const void *tm, const void *co, const void *qr, void *o, int32_t *sg, int32_t *stt,
+                            const int64_t *seg_off) {
+        csp::EvalArgs a = eval_args(s, tm, co, qr, num_queries, num_derivs, seg_off, stt);
+        a.out = o; a.seg_index = sg;
+        hipError_t e = csp::launch_eval(a, s.f32, st);
+        return e != hipSuccess ? hip_fail(e, "eval kernel launch") : (int)CSP_OK;
+    };
+    if (desc->mem_space == CSP_MEM_DEVICE) return launch(times, coeffs, query, out, seg_index, status, desc->seg_offsets);
+
+    Stage g(desc, s, st, nullptr, times, nullptr);
+    const size_t nq = (size_t)s.B * (size_t)num_queries;
+    const size_t i_co = g.in(coeffs, g.z.co), i_q = g.in(query, nq * s.elt);
+    const size_t o_out = g.out(out, nq * (size_t)num_derivs * 3 * s.elt), o_sg = g.out(seg_index, nq * 4);
+    const size_t o_st = g.out(status, (size_t)s.B * 4);
+    return g.run([&] {
+        return launch(g.ptr(g.tm), g.ptr(i_co), g.ptr(i_q), g.ptr(o_out), g.ptr<int32_t>(o_sg), g.ptr<int32_t>(o_st),
+                      g.ptr<const int64_t>(g.seg_off));
+    });
+}
+
+int csp_minsnap_eval_batch_vjp(const csp_minsnap_desc *desc, const void *times, const void *coeffs, const void *query,
+                               int64_t num_queries, int32_t num_derivs, const void *grad_out, void *grad_coeffs,
+                               void *grad_times, void *grad_query, int32_t *status, void *hip_stream) {
+    Shape s;
+    int rc = validate_eval(desc, s, num_queries, num_derivs);
+    if (rc != CSP_OK) return rc;
+    if (!grad_coeffs && !grad_times && !grad_query) return CSP_ERR_INVALID_ARG;
+    if (s.B == 0) return CSP_OK;
+    if (!times || !coeffs || (num_queries > 0 && (!query || !grad_out))) return CSP_ERR_INVALID_ARG;
+    if (desc->mem_space == CSP_MEM_DEVICE) {
+        const uintptr_t mask = s.f32 ? 7u : 15u;
+        if (((uintptr_t)coeffs & mask) || ((uintptr_t)grad_coeffs & mask)) return CSP_ERR_INVALID_ARG;
+    } else if (!offsets_ok(desc, s)) {
+        return CSP_ERR_INVALID_ARG;
+    }
+    rc = select_device(desc->device_id);
+    if (rc != CSP_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const auto launch = [&](const void *tm, const void *co, const void *qr, const void *go, void *gc, void *gt, void *gq,
+                            int32_t *stt, const int64_t *seg_off) {
+        csp::EvalArgs a = eval_args(s, tm, co, qr, num_queries, num_derivs, seg_off, stt);
+        a.grad_out = go; a.grad_coeffs = gc; a.grad_times = gt; a.grad_query = gq;
+        hipError_t e = csp::launch_eval_vjp(a, s.f32, st);
+        return e != hipSuccess ? hip_fail(e, "eval vjp kernel launch") : (int)CSP_OK;
+    };
+    if (desc->mem_space == CSP_MEM_DEVICE)
+        return launch(times, coeffs, query, grad_out, grad_coeffs, grad_times, grad_query, status, desc->seg_offsets);
+
+    Stage g(desc, s, st, nullptr, times, nullptr);
+    const size_t nq = (size_t)s.B * (size_t)num_queries;
+    const size_t i_co = g.in(coeffs, g.z.co), i_q = g.in(query, nq * s.elt);
+    const size_t i_go = g.in(grad_out, nq * (size_t)num_derivs * 3 * s.elt);
+    const size_t o_gc = g.out(grad_coeffs, g.z.co), o_gt = g.out(grad_times, g.z.tm), o_gq = g.out(grad_query, nq * s.elt);
+    const size_t o_st = g.out(status, (size_t)s.B * 4);
+    return g.run([&] {
+        return launch(g.ptr(g.tm), g.ptr(i_co), g.ptr(i_q), g.ptr(i_go), g.ptr(o_gc), g.ptr(o_gt), g.ptr(o_gq),
+                      g.ptr<int32_t>(o_st), g.ptr<const int64_t>(g.seg_off));
     });
 }
 

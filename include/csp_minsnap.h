@@ -93,7 +93,8 @@ enum { CSP_MEM_HOST = 0, CSP_MEM_DEVICE = 1 };
                                   middle coefficient alone (finite inputs of magnitude >~ 1e300) is not flagged there; the
                                   chunked, span and generic kernels test every stored coefficient                       */
 #define CSP_TRAJ_NOT_SPD 2     /* a pivot of the free-derivative Hessian R_PP was <= 0              */
-#define CSP_TRAJ_SKIPPED 4     /* csp_minsnap_solve_mixed only: the trajectory was NOT solved (its order is outside 2..5
+#define CSP_TRAJ_SKIPPED 4     /* csp_minsnap_solve_mixed (and a device-memory csp_minsnap_eval_batch[_vjp] given a ragged length outside
+                                  0..max_segments): the trajectory was NOT solved (its order is outside 2..5
                                   or its segment count outside 1..min(256, max_segments)); its coefficient block is left untouched (zero-filled with CSP_MEM_HOST) */
 #define CSP_TRAJ_NOT_CONVERGED 8 /* csp_minsnap_optimize_times_batch only: the stopping rule was not met (max_iters reached, or
                                   no decrease within rounding); the times returned are the last accepted ones          */
@@ -460,6 +461,75 @@ int csp_minsnap_generate_batch(const csp_minsnap_desc *desc, const void *waypoin
                                int32_t *counts, double *stats, void *times, void *coeffs, double *max_dev,
                                double *vel_zero_weight_out, int32_t *iterations, int32_t *status,
                                void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/* Position and its derivatives of every trajectory at arbitrary query times.  Works on any
+ * coefficient array in csp_minsnap_solve_batch's trajectory-major layout: the open-chain solve's, the periodic solve's
+ * (reduce t modulo the lap time first: there is no wrap-around here), a plan's.  Workspace-free.
+ *   desc       : dtype, order 2..5, batch, num_segments 1..1024 or a ragged batch (seg_offsets, max_segments <= 1024),
+ *                mem_space, device_id.  CSP_ERR_UNSUPPORTED for order 1, more than 1024 segments,
+ *                CSP_FLAG_SEGMENT_MAJOR and CSP_FLAG_F32_ARITH.  The weights and bc_per_trajectory are ignored.
+ *   times      : [B][S] segment durations T (ragged: concatenated, as for the solve)
+ *   coeffs     : [B][S][3][M], M = 2*order, highest power first (c_k * tau^(M-1-k)); 16-byte aligned (fp64) / 8-byte
+ *                (fp32), as the solve writes them
+ *   query      : [B][num_queries] global times t, measured from the trajectory's start; num_queries >= 0 is the same
+ *                for every trajectory
+ *   num_derivs : D in 1..5: position, velocity, acceleration, jerk, snap
+ *   out        : [B][num_queries][D][3]
+ *   seg_index  : optional [B][num_queries] i32, the segment j of every query
+ *   status     : optional [B] i32 CSP_TRAJ_* bits
+ * Every floating array is in the storage type desc->dtype; all arithmetic is fp64 (fp32 inputs convert exactly, outputs
+ * are rounded once when stored).  Per trajectory of S segments and per query t:
+ *   1. cum[0] = 0, cum[j+1] = cum[j] + T[j]: the left-to-right fp64 running sum, every addition rounded once.
+ *   2. t_c = min(max(t, 0), cum[S]).  t < 0 is "clamped low", t > cum[S] "clamped high"; t == cum[S] is in range.
+ *   3. j = the largest index with cum[j] <= t_c, at most S-1: a query on a knot belongs to the LATER segment, and a
+ *      zero-length segment is never selected unless it is the last one and t_c = cum[S].
+ *   4. tau = t_c - cum[j], one fp64 subtraction.
+ *   5. out[q][d][a] = sum_k c[j][a][k] * ff(p,d) * tau^(p-d), p = M-1-k, ff(p,d) = p(p-1)...(p-d+1) (0 for p < d),
+ *      0^0 = 1.  At tau = 0 the position is c[j][a][M-1] bit for bit (derivative d: ff(d,d) * c[j][a][M-1-d]).
+ *   6. seg_index[q] = j.
+ * Bad inputs are handled values, they never fault and never touch another trajectory's outputs:
+ *   - a query that is inf or NaN: its out rows are NaN and its seg_index is -1; the status is not changed;
+ *   - a trajectory with a T that is negative, inf or NaN: CSP_TRAJ_NONFINITE, all its out rows NaN, seg_index -1;
+ *   - a ragged trajectory with S_b = 0: status 0, out rows NaN, seg_index -1 (CSP_MEM_DEVICE: a length outside
+ *     0..max_segments is treated the same way and reported as CSP_TRAJ_SKIPPED; CSP_MEM_HOST: CSP_ERR_INVALID_ARG);
+ *   - CSP_TRAJ_NONFINITE is also set when a value stored for a finite query of a good trajectory is inf or NaN (NaN
+ *     coefficients, for instance).
+ * CSP_ERR_INVALID_ARG: num_derivs outside 1..5, num_queries < 0, a null times / coeffs, a null query / out with
+ * num_queries > 0, misaligned coeffs (CSP_MEM_DEVICE).  batch == 0 or num_queries == 0: CSP_OK, nothing is launched.
+ * Every argument check comes back before a device is looked for.
+ * CSP_MEM_HOST: staged through the cached arena, synchronous, the same bits as the device form.  CSP_MEM_DEVICE:
+ * asynchronous on `hip_stream`. */
+int csp_minsnap_eval_batch(const csp_minsnap_desc *desc, const void *times, const void *coeffs, const void *query,
+                           int64_t num_queries, int32_t num_derivs, void *out, int32_t *seg_index, int32_t *status,
+                           void *hip_stream);
+
+/* Reverse mode of csp_minsnap_eval_batch: given grad_out = dL/dout [B][num_queries][D][3], the vector-Jacobian products
+ * with respect to the coefficients, the segment times and the query times.  With tau_q, j_q of rules 1-4 above and
+ *   g_tau[q] = sum_{d,a} grad_out[q][d][a] * x_a^(d+1)(tau_q)          (derivatives up to order D)
+ *   grad_coeffs[j][a][k] = sum_{q: j_q = j} sum_d grad_out[q][d][a] * ff(p,d) * tau_q^(p-d), in ascending q.  EVERY record
+ *                  of the trajectory is written, zeros where no query falls: the caller pre-zeroes nothing.
+ *   grad_query[q] = g_tau[q] for a query in range, 0 for a clamped one.
+ *   grad_times[i] = - sum_{q in range, j_q > i} g_tau[q], plus sum_{q clamped high} g_tau[q] for i = S-1 only (a
+ *                  clamped-high query has tau = T[S-1] in exact arithmetic, so it moves grad_times[S-1] alone; a
+ *                  clamped-low one depends on no T).  Formed as per-segment sums in ascending q, then a suffix sum
+ *                  over the segments.
+ * This is the EXPLICIT dependence on `times` through tau only; the dependence of the coefficients on the times is
+ * csp_minsnap_solve_batch_vjp's, and the two add.  No atomics: two calls give identical bits, and each output has the
+ * same bits whichever of the others are asked for.
+ *   grad_coeffs : optional out, the layout and alignment of `coeffs`
+ *   grad_times  : optional out, the layout of `times`
+ *   grad_query  : optional out, [B][num_queries]; all three NULL: CSP_ERR_INVALID_ARG
+ *   status      : optional [B] i32
+ * Bad inputs: an inf / NaN query contributes nothing to grad_coeffs and grad_times, its grad_query is NaN; a trajectory
+ * with a negative, inf or NaN T gets CSP_TRAJ_NONFINITE and NaN in all its grad_coeffs, grad_times and grad_query rows;
+ * a ragged trajectory with S_b = 0 gets status 0 and zeros in its grad_query rows (it has no other rows);
+ * CSP_TRAJ_NONFINITE is also set when a gradient stored for a good trajectory (grad_query of a finite query) is inf/NaN.
+ * Scope, CSP_ERR_UNSUPPORTED and CSP_ERR_INVALID_ARG cases as above (grad_out takes the place of out; a misaligned
+ * grad_coeffs counts like misaligned coeffs).  batch == 0: CSP_OK.  num_queries == 0 still writes zero grad_coeffs and
+ * grad_times.  CSP_MEM_HOST: staged, synchronous, the device form's bits.  CSP_MEM_DEVICE: asynchronous on `hip_stream`. */
+int csp_minsnap_eval_batch_vjp(const csp_minsnap_desc *desc, const void *times, const void *coeffs, const void *query,
+                               int64_t num_queries, int32_t num_derivs, const void *grad_out, void *grad_coeffs,
+                               void *grad_times, void *grad_query, int32_t *status, void *hip_stream);
 
 /* Upper bound of the samples any trajectory of the batch can produce (every candidate of the sampling loop,
  * minimum_snap.cpp:126-161, plus the first and the last point), from HOST-resident waypoints: a `capacity` that
