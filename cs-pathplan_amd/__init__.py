@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "csp_minsnap_timeopt_workspace_bytes",
     "csp_minsnap_solve_periodic_batch", "csp_minsnap_periodic_workspace_bytes",
     "csp_minsnap_solve_periodic_batch_vjp", "csp_minsnap_periodic_vjp_workspace_bytes",
+    "csp_minsnap_solve_knots_batch", "csp_minsnap_knots_workspace_bytes",
     "csp_minsnap_eval_batch", "csp_minsnap_eval_batch_vjp",
     "csp_minsnap_solve_mixed", "csp_minsnap_mixed_workspace_bytes", "csp_minsnap_solve_multi",
     "csp_minsnap_plan_batch", "csp_minsnap_plan_workspace_bytes", "csp_minsnap_sample_batch",
@@ -137,6 +138,8 @@ _PROTOTYPES = {
     "csp_minsnap_periodic_workspace_bytes": (_SZ, [_D]),
     "csp_minsnap_solve_periodic_batch_vjp": (_I, [_D] + [_P] * 8 + [_SZ, _P]),
     "csp_minsnap_periodic_vjp_workspace_bytes": (_SZ, [_D]),
+    "csp_minsnap_solve_knots_batch": (_I, [_D] + [_P] * 8 + [_SZ, _P]),
+    "csp_minsnap_knots_workspace_bytes": (_SZ, [_D]),
     "csp_minsnap_eval_batch": (_I, [_D, _P, _P, _P, _I64, _I32, _P, _P, _P, _P]),
     "csp_minsnap_eval_batch_vjp": (_I, [_D, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     "csp_minsnap_solve_multi": (_I, [_D, _I] + [_P] * 7),
@@ -718,6 +721,82 @@ def solve_periodic_batch_vjp(waypoints, times, grad_coeffs, grad_cost=None, orde
     _check(_lib.csp_minsnap_solve_periodic_batch_vjp(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(gco), p(gj), p(gwp),
                                                      p(gtm), p(stt), wsp, need, mem.stream(stream)))
     return PeriodicVjpResult(gwp, gtm, stt)
+
+
+def knots_workspace_bytes(desc):
+    return int(_lib.csp_minsnap_knots_workspace_bytes(ctypes.byref(desc)))
+
+
+class KnotsResult:
+    """solve_knots_batch: coeffs ([B,S,3,2o], or [sum S_b,3,2o] ragged), status [B] i32, cost [B] f64 (or None)."""
+    __slots__ = ("coeffs", "status", "cost")
+
+    def __init__(self, coeffs, status, cost):
+        self.coeffs, self.status, self.cost = coeffs, status, cost
+
+
+def knots_from_bc(bc, num_segments, order, batch=None):
+    """(knot_mask, knot_values) of the standard problem of solve_batch for solve_knots_batch: both end knots carry every
+    bit below order-1 (velocity and acceleration from bc, higher derivatives 0), every interior knot is free.
+    bc: [4,3] / [1,4,3] shared (then `batch` trajectories, default 1) or [B,4,3]; None = zeros.  Rows: start vel, end vel,
+    start acc, end acc.  Returns numpy arrays: mask [B,S+1] uint8, values [B,S+1,order-1,3] in bc's dtype (float64 unless
+    bc is float32).  A ragged batch is built per trajectory and concatenated along the knot axis."""
+    order, S = int(order), int(num_segments)
+    if order < 2 or S < 1:
+        raise ValueError("knots_from_bc needs order >= 2 and num_segments >= 1")
+    if bc is None:
+        bc = np.zeros((1, 4, 3))
+    if _is_torch(bc):
+        bc = bc.detach().cpu().numpy()
+    bc = np.asarray(bc)
+    bc = bc.astype(np.float32 if bc.dtype == np.float32 else np.float64, copy=False).reshape(-1, 4, 3)
+    B = int(batch) if batch is not None else bc.shape[0]
+    if bc.shape[0] not in (1, B):
+        raise ValueError("bc must be [4,3], [1,4,3] or [B,4,3]")
+    n = order - 1
+    mask = np.zeros((B, S + 1), np.uint8)
+    mask[:, 0] = mask[:, S] = (1 << n) - 1
+    values = np.zeros((B, S + 1, n, 3), bc.dtype)
+    values[:, 0, 0], values[:, S, 0] = bc[:, 0], bc[:, 1]
+    if n > 1:
+        values[:, 0, 1], values[:, S, 1] = bc[:, 2], bc[:, 3]
+    return mask, values
+
+
+def solve_knots_batch(waypoints, times, knot_mask, knot_values, order=4, vel_zero_weight=0.0, seg_offsets=None,
+                      max_segments=None, want_cost=False, workspace=None, stream=None, vel_zero_weight_per_traj=None):
+    """The open-chain minimum-snap solve with per-knot derivative constraints (csp_minsnap_solve_knots_batch, DESIGN.md
+    §20).  Positions are fixed at every waypoint; knot_mask [B,S+1] uint8 says per knot (waypoint) which derivatives are
+    fixed: bit r set = derivative r+1 equals knot_values[b,k,r,:] ([B,S+1,order-1,3], the storage dtype of waypoints), bit
+    clear = free, chosen by the solve (the entry is then never read).  A free end is an end knot with mask 0; the
+    standard problem's mask is knots_from_bc's.  Ragged: waypoints [sum(S_b+1),3], times [sum S_b], knot_mask
+    [sum(S_b+1)] and knot_values [sum(S_b+1),order-1,3] with seg_offsets [B+1].
+    numpy arrays -> host memory, torch CUDA tensors -> device memory (asynchronous on the current stream); beside device
+    waypoints, knot_mask and knot_values may be numpy arrays (knots_from_bc's) and are copied to the device.
+    Returns KnotsResult(coeffs, status, cost): the coefficients have solve_batch's trajectory-major layout, so
+    eval_batch, sample_batch and every other consumer of solve_batch's coefficients read them unchanged.  A trajectory
+    with fewer constraints (its S+1 positions plus its set mask bits) than `order` has no unique minimiser: status
+    TRAJ_NOT_SPD, NaN coefficients and cost.  want_cost adds the snap cost J of snap_cost_batch at the optimum."""
+    ci = _CallInputs(waypoints, times, None, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    mem, p = ci.mem, ci.mem.ptr
+    n = int(order) - 1
+    knots = ci.total + ci.B
+    if mem.mem_space == MEM_DEVICE:   # knots_from_bc returns numpy arrays: they may be passed beside device waypoints
+        knot_mask, knot_values = (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+                                  for a in (knot_mask, knot_values))
+    mk, kv = mem.contig(knot_mask, "u8"), mem.contig(knot_values, ci.io)
+    if math.prod(mk.shape) != knots:
+        raise ValueError("knot_mask must hold %d elements (one per waypoint)" % knots)
+    if math.prod(kv.shape) != knots * n * 3:
+        raise ValueError("knot_values must hold %d elements ([knots][order-1][3])" % (knots * n * 3))
+    desc = ci.desc(order, False, 0.0, vel_zero_weight)
+    co = mem.empty(ci.coeffs_shape(order), ci.io)
+    cost = mem.empty((ci.B,), "f64") if want_cost else None
+    stt = mem.empty((ci.B,), "i32")
+    wsp, need = mem.workspace(knots_workspace_bytes(desc), workspace)
+    _check(_lib.csp_minsnap_solve_knots_batch(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(mk), p(kv), p(co), p(cost),
+                                              p(stt), wsp, need, mem.stream(stream)))
+    return KnotsResult(co, stt, cost)
 
 
 def _make_periodic_autograd_fn():

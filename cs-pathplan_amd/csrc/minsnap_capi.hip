@@ -9,6 +9,7 @@
 #include "minsnap_launch.h"
 #include "minsnap_eval.h"
 #include "minsnap_periodic_vjp.h"
+#include "minsnap_knots.h"
 #include "minsnap_vjp.h"
 #include "minsnap_hoststage.h"
 #include "minsnap_timealloc.h"
@@ -189,7 +190,11 @@ struct Stage {
     const Sizes z;
     size_t wp, tm, bc, seg_off, vw_per;
     Stage(const csp_minsnap_desc *d, const Shape &s, hipStream_t st, const void *waypoints, const void *times, const void *bc_host)
-        : hc(current_device(), st), z(sizes_of(d, s, bc_host == nullptr)) {
+        : Stage(d, s, st, waypoints, times, bc_host, bc_host == nullptr) {}
+    // an open chain without a bc (csp_minsnap_solve_knots_batch) says so itself
+    Stage(const csp_minsnap_desc *d, const Shape &s, hipStream_t st, const void *waypoints, const void *times, const void *bc_host,
+          bool closed_loop)
+        : hc(current_device(), st), z(sizes_of(d, s, closed_loop)) {
         wp = in(waypoints, z.wp);
         tm = in(times, z.tm);
         bc = in(bc_host, z.bc);
@@ -702,6 +707,26 @@ int dispatch_periodic_vjp(const csp_minsnap_desc *d, const Shape &s, const void 
     a.B = s.B; a.S = s.S; a.order = s.order;
     hipError_t e = csp::launch_periodic_vjp(a, s.f32, st);
     if (e != hipSuccess) return hip_fail(e, "periodic vjp kernel launch");
+    return CSP_OK;
+}
+
+// csp_minsnap_solve_knots_batch: the VJP's scope (validate_vjp); bc_per_trajectory is ignored (there is no bc).  Knots
+// 0..Smax of every trajectory.
+size_t knots_ws_bytes(const Shape &s) {
+    return align_up((size_t)(s.Smax + 1) * csp::knots_ws_entries(s.order) * (size_t)s.B * 8, 256);
+}
+
+int dispatch_knots(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const uint8_t *mask,
+                   const void *values, void *co, double *cost, int32_t *status, const int64_t *seg_off, const double *vw_per,
+                   void *ws, hipStream_t st) {
+    csp::KnotsArgs a{};
+    a.wp = wp; a.times = tm; a.mask = mask; a.values = values; a.coeffs = co; a.cost = cost; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.ws = ws; a.vw_per = vw_per;
+    a.vel_zero_weight = d->vel_zero_weight;
+    a.B = s.B; a.S = s.S; a.Smax = s.Smax; a.order = s.order;
+    hipError_t e = csp::launch_knots(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, "knots kernel launch");
     return CSP_OK;
 }
 
@@ -1705,6 +1730,49 @@ int csp_minsnap_solve_periodic_batch_vjp(const csp_minsnap_desc *desc, const voi
         return dispatch_periodic_vjp(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(o_gc), g.ptr<const double>(o_gj), g.ptr(o_gw),
                                      g.ptr(o_gt), g.ptr<int32_t>(o_st), g.ptr<const int64_t>(g.seg_off),
                                      g.ptr<const double>(g.vw_per), g.ptr(o_ws), st);
+    });
+}
+
+size_t csp_minsnap_knots_workspace_bytes(const csp_minsnap_desc *desc) {
+    Shape s;
+    if (validate_vjp(desc, s) != CSP_OK) return 0;
+    return knots_ws_bytes(s);
+}
+
+int csp_minsnap_solve_knots_batch(const csp_minsnap_desc *desc, const void *waypoints, const void *times,
+                                  const uint8_t *knot_mask, const void *knot_values, void *coeffs, double *cost,
+                                  int32_t *status, void *workspace, size_t workspace_bytes, void *hip_stream) {
+    Shape s;
+    int rc = validate_vjp(desc, s);
+    if (rc != CSP_OK) return rc;
+    if (s.B == 0) return CSP_OK;
+    if (!waypoints || !times || !knot_mask || !knot_values || !coeffs) return CSP_ERR_INVALID_ARG;
+    const size_t n_ws = knots_ws_bytes(s);
+    if (desc->mem_space == CSP_MEM_DEVICE) {
+        if (!workspace || workspace_bytes < n_ws) return CSP_ERR_WORKSPACE;
+        if ((uintptr_t)workspace & 7u) return CSP_ERR_WORKSPACE;
+        if ((uintptr_t)coeffs & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // records are stored as 2-element vectors
+    } else if (!offsets_ok(desc, s)) {
+        return CSP_ERR_INVALID_ARG;
+    }
+    rc = select_device(desc->device_id);
+    if (rc != CSP_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+
+    if (desc->mem_space == CSP_MEM_DEVICE)
+        return dispatch_knots(desc, s, waypoints, times, knot_mask, knot_values, coeffs, cost, status, desc->seg_offsets,
+                              desc->vel_zero_weight_per_traj, workspace, st);
+
+    // CSP_MEM_HOST: as csp_minsnap_solve_batch, one mask byte and order-1 value rows per waypoint and no bc
+    Stage g(desc, s, st, waypoints, times, nullptr, false);
+    const size_t n_knots = (size_t)(g.z.total_seg + s.B);
+    const size_t o_mk = g.in(knot_mask, n_knots), o_kv = g.in(knot_values, n_knots * (size_t)(s.order - 1) * 3 * s.elt);
+    const size_t o_co = g.out(coeffs, g.z.co), o_c = g.out(cost, (size_t)s.B * 8);
+    const size_t o_st = g.out(status, (size_t)s.B * 4), o_ws = g.hc.scratch(n_ws);
+    return g.run([&] {
+        return dispatch_knots(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr<const uint8_t>(o_mk), g.ptr(o_kv), g.ptr(o_co),
+                              g.ptr<double>(o_c), g.ptr<int32_t>(o_st), g.ptr<const int64_t>(g.seg_off),
+                              g.ptr<const double>(g.vw_per), g.ptr(o_ws), st);
     });
 }
 

@@ -338,6 +338,51 @@ int csp_minsnap_solve_periodic_batch_vjp(const csp_minsnap_desc *desc, const voi
  * descriptor). */
 size_t csp_minsnap_periodic_vjp_workspace_bytes(const csp_minsnap_desc *desc);
 
+/* The open-chain minimum-snap solve with PER-KNOT derivative constraints: positions are fixed at every
+ * waypoint as in csp_minsnap_solve_batch, and every derivative 1..order-1 of every knot (waypoint) is either fixed to a
+ * given value or free, chosen by the solve.  Free ends, a velocity pinned at an interior waypoint, "come to rest at
+ * waypoint k" are masks.  There is no bc argument: the standard problem of csp_minsnap_solve_batch is the mask with all
+ * order-1 bits set at both end knots (values: velocity and acceleration from bc, higher rows zero) and 0 at every
+ * interior knot.  One lane per trajectory, one block-LDL^T sweep over the S+1 knots shared by the three axes, the factors
+ * in `workspace`; no atomics, results bit-identical run to run.
+ *   desc        : the scope of csp_minsnap_cost_batch (orders 2..5, any S >= 1, uniform or ragged, CSP_DTYPE_F64 or
+ *                 CSP_DTYPE_F32 with fp64 arithmetic, vel_zero_weight scalar or per trajectory).  CSP_ERR_UNSUPPORTED for
+ *                 order 1 or 6+, path_weight != 0, CSP_FLAG_SEGMENT_MAJOR and CSP_FLAG_F32_ARITH.  bc_per_trajectory is
+ *                 ignored.
+ *   waypoints   : [B][S+1][3]; the knots of trajectory b.  Ragged: knot k of trajectory b is row seg_offsets[b] + b + k
+ *   times       : [B][S]
+ *   knot_mask   : [B][S+1] u8, the knots' layout (ragged: index seg_offsets[b] + b + k).  Bit r (r = 0 .. order-2) set:
+ *                 derivative r+1 at that knot is fixed to knot_values[knot][r][0..2]; clear: it is free.  The three axes
+ *                 share a knot's mask.  Bits from order-1 upward are ignored.
+ *   knot_values : [knots][order-1][3] in the storage type of desc->dtype.  An entry whose mask bit is clear is never
+ *                 used: NaN or inf there reaches no output.
+ *   coeffs      : out, [B][S][3][2*order], the record format and trajectory-major layout of csp_minsnap_solve_batch (so
+ *                 csp_minsnap_eval_batch and csp_minsnap_sample_batch read it unchanged); 16-byte aligned (fp64) / 8-byte
+ *                 (fp32)
+ *   cost        : optional out, [B] f64: J at the optimum with the definition of csp_minsnap_cost_batch, the
+ *                 vel_zero_weight term included.  The coefficients are the same bits with or without it.
+ *   status      : optional out, [B] i32.  CSP_TRAJ_NOT_SPD: a pivot <= 0, a segment time that is not > 0 (its Hessian
+ *                 block is not positive semi-definite even where pinned neighbours leave every pivot positive), or a
+ *                 trajectory whose constraint count -- its
+ *                 S+1 positions plus the set mask bits below order-1, summed over its knots -- is below the order: a
+ *                 non-zero polynomial of degree < order then costs nothing and the minimiser is not unique.  That case
+ *                 is decided by the count before the sweep; coefficients and cost are NaN.  CSP_TRAJ_NONFINITE: a stored
+ *                 coefficient or J is inf/NaN.  A ragged trajectory with S_b = 0 gets cost 0 and status 0; nothing else
+ *                 is written for it.  A ragged trajectory longer than max_segments (CSP_MEM_DEVICE; CSP_MEM_HOST:
+ *                 CSP_ERR_INVALID_ARG) gets CSP_TRAJ_SKIPPED and a NaN cost, its coefficients are not written.  A bad
+ *                 trajectory does not change any output of another one.
+ *   workspace   : device scratch of csp_minsnap_knots_workspace_bytes(desc) bytes (CSP_MEM_DEVICE, 8-byte aligned); may
+ *                 be NULL/0 with CSP_MEM_HOST.  With o = order, Smax = num_segments (uniform) or max_segments (ragged):
+ *                   round_up_256((Smax + 1) * ((o-1)^2 + 3(o-1)) * B * 8)
+ * Arguments (NULL waypoints / times / knot_mask / knot_values / coeffs, workspace size and alignment and the alignment of
+ * coeffs of a device call) are checked before a device is looked for.
+ * CSP_MEM_HOST: staged through the cached arena, synchronous.  CSP_MEM_DEVICE: asynchronous on `hip_stream`. */
+int csp_minsnap_solve_knots_batch(const csp_minsnap_desc *desc, const void *waypoints, const void *times,
+                                  const uint8_t *knot_mask, const void *knot_values, void *coeffs, double *cost,
+                                  int32_t *status, void *workspace, size_t workspace_bytes, void *hip_stream);
+/* Device scratch bytes csp_minsnap_solve_knots_batch needs (formula above; 0 for an invalid or unsupported descriptor). */
+size_t csp_minsnap_knots_workspace_bytes(const csp_minsnap_desc *desc);
+
 /* The same solve spread over `ngpu` devices of this node from ONE process (the reference planner
  * is a single C++ process).  Trajectories are independent
  * (minimum_snap.cpp has no cross-trajectory term), so the batch is cut into `ngpu` contiguous shards, shard g on the
