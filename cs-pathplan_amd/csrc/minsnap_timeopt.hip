@@ -76,10 +76,10 @@ __device__ int cost_pass(const IO *wp, const TT *tm, int64_t ts, const double (&
                 }
 #pragma unroll
                 for (int ax = 0; ax < 3; ++ax) {
-                    double v = left.ep0[r] * Pp[ax];
-                    v = fma_<double>(left.ep1[r], Pc[ax], v);
-                    v = fma_<double>(right.sp0[r], Pc[ax], v);
-                    v = fma_<double>(right.sp1[r], Pn[ax], v);
+                    // Qt annihilates constants (ep0 = -ep1, sp0 = -sp1): the two legs, not four nearly opposite
+                    // products of the waypoints, which lose |P| / |leg| digits
+                    double v = left.ep1[r] * (Pc[ax] - Pp[ax]);
+                    v = fma_<double>(right.sp1[r], Pn[ax] - Pc[ax], v);
 #pragma unroll
                     for (int j = 0; j < N; ++j) v = fma_<double>(left.se[j][r], z[j][ax], v);
                     Bm[r][N + ax] = -v;

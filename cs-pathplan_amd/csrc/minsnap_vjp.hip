@@ -23,7 +23,7 @@
 // gradients.
 //
 // JBAR without PBAR (grad_coeffs null, never read): d_bar = 0 and lambda = 0.  The cost kernel's sweep -- three primal
-// right-hand sides, (o-1)^2 + 3(o-1) workspace entries per knot, waypoints relative to the trajectory's first.
+// right-hand sides, (o-1)^2 + 3(o-1) workspace entries per knot.
 //
 // Mapping as minsnap_generic.hip / minsnap_timeopt.hip: one lane per trajectory, workgroups of one wave, the block-LDL^T
 // factors in a coalesced [waypoint][entry][trajectory] workspace, the next step's inputs requested one step ahead, loops
@@ -36,17 +36,6 @@
 namespace csp {
 
 using namespace vjpk;   // minsnap_vjp_device.h: vload3, load_rec, dbar_axis, powers, wave_sum
-
-namespace {
-
-// a waypoint relative to `org` (the trajectory's first waypoint in the cost-only kernel: J does not depend on a
-// translation and the right-hand sides then cancel less; zero with PBAR, where the coefficients need absolute positions)
-template <typename IO>
-__device__ __forceinline__ void tload3(const IO *p, const double (&org)[3], double (&v)[3]) {
-    v[0] = double(p[0]) - org[0]; v[1] = double(p[1]) - org[1]; v[2] = double(p[2]) - org[2];
-}
-
-}  // namespace
 
 template <int O, typename IO, bool PBAR, bool JBAR>
 __global__ void __launch_bounds__(64) minsnap_vjp_kernel(CostVjpArgs a) {
@@ -122,8 +111,6 @@ __global__ void __launch_bounds__(64) minsnap_vjp_kernel(CostVjpArgs a) {
                     for (int ax = 0; ax < 3; ++ax) x[r][ax] = held[end][r][ax];
             }
         };
-        R org[3] = {R(0), R(0), R(0)};
-        if (!PBAR) { org[0] = R(wp[0]); org[1] = R(wp[1]); org[2] = R(wp[2]); }
         R *ws = (R *)a.ws + b;
         const R vw = (R)(a.vw_per ? a.vw_per[b] : a.vel_zero_weight);
 
@@ -142,9 +129,9 @@ __global__ void __launch_bounds__(64) minsnap_vjp_kernel(CostVjpArgs a) {
                 }
             }
             R Pp[3], Pc[3], Pn[3], Pnn[3] = {R(0), R(0), R(0)};
-            tload3<IO>(wp, org, Pp);
-            tload3<IO>(wp + 3, org, Pc);
-            tload3<IO>(wp + 6, org, Pn);
+            vload3<IO, R>(wp, Pp);
+            vload3<IO, R>(wp + 3, Pc);
+            vload3<IO, R>(wp + 6, Pn);
             R Tn = R(tm[1]), Tnn = R(1);
             R pbn[3][M], pbnn[3][M];
             // segment 0: the end part of its d_bar is the left contribution of waypoint 1
@@ -167,7 +154,7 @@ __global__ void __launch_bounds__(64) minsnap_vjp_kernel(CostVjpArgs a) {
             seg_blocks<O, R, false>(R(tm[0]), vw, R(0), 0, Pp, Pc, left);
             for (int k = 1; k < S; ++k) {
                 if (k + 1 < S) {  // prefetch waypoint k+2, time k+1 (and p_bar of segment k+1)
-                    tload3<IO>(wp + 3 * (k + 2), org, Pnn);
+                    vload3<IO, R>(wp + 3 * (k + 2), Pnn);
                     Tnn = R(tm[k + 1]);
                     if (PBAR) load_rec<O, IO, R>(gco + (int64_t)(k + 1) * 3 * M, pbnn);
                 }
@@ -198,10 +185,10 @@ __global__ void __launch_bounds__(64) minsnap_vjp_kernel(CostVjpArgs a) {
                     }
 #pragma unroll
                     for (int ax = 0; ax < 3; ++ax) {
-                        R v = left.ep0[r] * Pp[ax];
-                        v = fma_<R>(left.ep1[r], Pc[ax], v);
-                        v = fma_<R>(right.sp0[r], Pc[ax], v);
-                        v = fma_<R>(right.sp1[r], Pn[ax], v);
+                        // Qt annihilates constants (ep0 = -ep1, sp0 = -sp1): the two legs, not four nearly opposite
+                        // products of the waypoints themselves, which lose |P| / |leg| digits
+                        R v = left.ep1[r] * (Pc[ax] - Pp[ax]);
+                        v = fma_<R>(right.sp1[r], Pn[ax] - Pc[ax], v);
                         if constexpr (JBAR) {
 #pragma unroll
                             for (int j = 0; j < N; ++j) v = fma_<R>(left.se[j][r], z[j][ax], v);
@@ -261,7 +248,7 @@ __global__ void __launch_bounds__(64) minsnap_vjp_kernel(CostVjpArgs a) {
         R nanacc = R(0);
         R carry[3] = {R(0), R(0), R(0)};   // start-of-segment part of waypoint k+1's gradient (segment k+1)
         R Tk = R(tm[S - 1]), P0[3], P1[3], wz[E], pb[3][M];
-        // positions enter the J part as P1 - P0 only, and the p_bar part (org = 0) as they are: no translation here
+        // positions enter as P1 - P0 only
         vload3<IO, R>(wp + 3 * (S - 1), P0);
         vload3<IO, R>(wp + 3 * S, P1);
         if (PBAR) load_rec<O, IO, R>(gco + (int64_t)(S - 1) * 3 * M, pb);
@@ -355,8 +342,10 @@ __global__ void __launch_bounds__(64) minsnap_vjp_kernel(CostVjpArgs a) {
                 }
                 if (PBAR) {
                     R d[M], c[M], db[M], lt[M];
-                    d[0] = P0[ax];
-                    d[O] = P1[ax];
+                    // the segment's start as origin: positions carry weight zero in every term below but the Qt
+                    // products, which annihilate constants, and only the constant coefficient of c depends on it
+                    d[0] = R(0);
+                    d[O] = P1[ax] - P0[ax];
                     lt[0] = R(0);
                     lt[O] = R(0);
 #pragma unroll

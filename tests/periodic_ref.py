@@ -125,9 +125,10 @@ def _kkt(o, path, T, w, nm):
     return K, R
 
 
-def solve(order, path, time, w=0.0, dps=None):
+def solve(order, path, time, w=0.0, dps=None, raw=False):
     """Returns (coeffs [S,3,2o] highest power first, J, dJ/dT [S]) as float64.  path [S,3], time [S].  dps: mpmath digits
-    (None = numpy fp64)."""
+    (None = numpy fp64).  raw: keep the numbers of the solve (mpmath under dps) in object arrays, for checks that need
+    more than a double."""
     o = int(order)
     m = 2 * o
     S = len(time)
@@ -166,6 +167,10 @@ def solve(order, path, time, w=0.0, dps=None):
                 for r in range(0, o):
                     gj += lam[q0 + 1 + r][ax] * deriv(cc, r + 1, T[j])
                 g[j] += gj
+        if raw:
+            co = np.array([[[c[j][ax][m - 1 - i] if i < m - 1 else nm.num(path[j][ax]) for i in range(m)] for ax in range(3)]
+                           for j in range(S)], dtype=object)
+            return co, J, np.array(g, dtype=object)
         coeffs = np.zeros((S, 3, m))
         for j in range(S):
             for ax in range(3):

@@ -262,7 +262,7 @@ def loop_errors(c, J, g, rc, rJ, rg):
 
 # Seeds: condition (c) of tests/test_spread_ref.py compares two results rounded to double, so where e_cpu64 is within a
 # factor of two of its 1e-14 threshold one ulp of output rounding can break it; the chunked and generic seeds were moved
-# until no draw sits there (the issue's rule: change the seed, not the condition)
+# until no draw sits there (the seed changes, never the condition)
 _FAMILY_SEED = {"fixed": 11, "fixedpath": 12, "chunked": 43, "span": 14, "generic": 25, "mixed": 16, "periodic": 17, "multi": 18}
 
 
