@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "csp_minsnap_solve_periodic_batch", "csp_minsnap_periodic_workspace_bytes",
     "csp_minsnap_solve_periodic_batch_vjp", "csp_minsnap_periodic_vjp_workspace_bytes",
     "csp_minsnap_solve_knots_batch", "csp_minsnap_knots_workspace_bytes",
+    "csp_minsnap_solve_knots_batch_vjp", "csp_minsnap_knots_vjp_workspace_bytes",
     "csp_minsnap_eval_batch", "csp_minsnap_eval_batch_vjp",
     "csp_minsnap_solve_mixed", "csp_minsnap_mixed_workspace_bytes", "csp_minsnap_solve_multi",
     "csp_minsnap_plan_batch", "csp_minsnap_plan_workspace_bytes", "csp_minsnap_sample_batch",
@@ -140,6 +141,8 @@ _PROTOTYPES = {
     "csp_minsnap_periodic_vjp_workspace_bytes": (_SZ, [_D]),
     "csp_minsnap_solve_knots_batch": (_I, [_D] + [_P] * 8 + [_SZ, _P]),
     "csp_minsnap_knots_workspace_bytes": (_SZ, [_D]),
+    "csp_minsnap_solve_knots_batch_vjp": (_I, [_D] + [_P] * 11 + [_SZ, _P]),
+    "csp_minsnap_knots_vjp_workspace_bytes": (_SZ, [_D, _I]),
     "csp_minsnap_eval_batch": (_I, [_D, _P, _P, _P, _I64, _I32, _P, _P, _P, _P]),
     "csp_minsnap_eval_batch_vjp": (_I, [_D, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     "csp_minsnap_solve_multi": (_I, [_D, _I] + [_P] * 7),
@@ -763,6 +766,22 @@ def knots_from_bc(bc, num_segments, order, batch=None):
     return mask, values
 
 
+def _knot_arrays(ci, knot_mask, knot_values, order):
+    """knot_mask / knot_values of a knots call, contiguous in the call's memory space and checked against its knots."""
+    mem = ci.mem
+    n = int(order) - 1
+    knots = ci.total + ci.B
+    if mem.mem_space == MEM_DEVICE:   # knots_from_bc returns numpy arrays: they may be passed beside device waypoints
+        knot_mask, knot_values = (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
+                                  for a in (knot_mask, knot_values))
+    mk, kv = mem.contig(knot_mask, "u8"), mem.contig(knot_values, ci.io)
+    if math.prod(mk.shape) != knots:
+        raise ValueError("knot_mask must hold %d elements (one per waypoint)" % knots)
+    if math.prod(kv.shape) != knots * n * 3:
+        raise ValueError("knot_values must hold %d elements ([knots][order-1][3])" % (knots * n * 3))
+    return mk, kv
+
+
 def solve_knots_batch(waypoints, times, knot_mask, knot_values, order=4, vel_zero_weight=0.0, seg_offsets=None,
                       max_segments=None, want_cost=False, workspace=None, stream=None, vel_zero_weight_per_traj=None):
     """The open-chain minimum-snap solve with per-knot derivative constraints (csp_minsnap_solve_knots_batch, DESIGN.md
@@ -779,16 +798,7 @@ def solve_knots_batch(waypoints, times, knot_mask, knot_values, order=4, vel_zer
     TRAJ_NOT_SPD, NaN coefficients and cost.  want_cost adds the snap cost J of snap_cost_batch at the optimum."""
     ci = _CallInputs(waypoints, times, None, seg_offsets, max_segments, vel_zero_weight_per_traj)
     mem, p = ci.mem, ci.mem.ptr
-    n = int(order) - 1
-    knots = ci.total + ci.B
-    if mem.mem_space == MEM_DEVICE:   # knots_from_bc returns numpy arrays: they may be passed beside device waypoints
-        knot_mask, knot_values = (torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a
-                                  for a in (knot_mask, knot_values))
-    mk, kv = mem.contig(knot_mask, "u8"), mem.contig(knot_values, ci.io)
-    if math.prod(mk.shape) != knots:
-        raise ValueError("knot_mask must hold %d elements (one per waypoint)" % knots)
-    if math.prod(kv.shape) != knots * n * 3:
-        raise ValueError("knot_values must hold %d elements ([knots][order-1][3])" % (knots * n * 3))
+    mk, kv = _knot_arrays(ci, knot_mask, knot_values, order)
     desc = ci.desc(order, False, 0.0, vel_zero_weight)
     co = mem.empty(ci.coeffs_shape(order), ci.io)
     cost = mem.empty((ci.B,), "f64") if want_cost else None
@@ -797,6 +807,123 @@ def solve_knots_batch(waypoints, times, knot_mask, knot_values, order=4, vel_zer
     _check(_lib.csp_minsnap_solve_knots_batch(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(mk), p(kv), p(co), p(cost),
                                               p(stt), wsp, need, mem.stream(stream)))
     return KnotsResult(co, stt, cost)
+
+
+def knots_vjp_workspace_bytes(desc, with_grad_coeffs=True):
+    return int(_lib.csp_minsnap_knots_vjp_workspace_bytes(ctypes.byref(desc), 1 if with_grad_coeffs else 0))
+
+
+class KnotsVjpResult:
+    """Gradients of solve_knots_batch_vjp; a gradient that was not asked for is None."""
+    __slots__ = ("waypoints", "times", "knot_values", "status")
+
+    def __init__(self, waypoints, times, knot_values, status):
+        self.waypoints, self.times, self.knot_values, self.status = waypoints, times, knot_values, status
+
+
+_KNOTS_VJP_WANT = ("waypoints", "times", "knot_values")
+
+
+def solve_knots_batch_vjp(waypoints, times, knot_mask, knot_values, grad_coeffs=None, grad_cost=None, order=4,
+                          vel_zero_weight=0.0, seg_offsets=None, max_segments=None, vel_zero_weight_per_traj=None,
+                          want=_KNOTS_VJP_WANT, want_status=False, workspace=None, stream=None):
+    """Vector-Jacobian product of solve_knots_batch (csp_minsnap_solve_knots_batch_vjp): given grad_coeffs
+    = dL/dcoeffs in the layout of that call's coefficients and / or grad_cost = dL/dcost [B] (at least one), returns
+    KnotsVjpResult(dL/dwaypoints, dL/dtimes, dL/dknot_values, status) for the names in `want`.  dL/dknot_values is exactly
+    0.0 at every slot whose mask bit is clear.  Without grad_coeffs the three-column kernel runs and grad_coeffs is never
+    allocated or read.  Inputs as in solve_knots_batch: numpy arrays -> CSP_MEM_HOST, torch CUDA tensors ->
+    CSP_MEM_DEVICE (knot_mask and knot_values may be numpy arrays beside device waypoints)."""
+    want = tuple(want)
+    for w in want:
+        if w not in _KNOTS_VJP_WANT:
+            raise ValueError("want: a subset of %r" % (_KNOTS_VJP_WANT,))
+    if grad_coeffs is None and grad_cost is None:
+        raise ValueError("solve_knots_batch_vjp needs grad_coeffs, grad_cost or both")
+    ci = _CallInputs(waypoints, times, None, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    mem, p = ci.mem, ci.mem.ptr
+    mk, kv = _knot_arrays(ci, knot_mask, knot_values, order)
+    gco = None
+    if grad_coeffs is not None:
+        gco = mem.contig(grad_coeffs, ci.io)
+        if mem.mem_space == MEM_DEVICE and gco.data_ptr() % 16:   # the kernel reads it in 16-byte pieces (host memory is staged)
+            gco = gco.clone()
+        n = ci.total * 3 * 2 * int(order)
+        if math.prod(gco.shape) != n:
+            raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % n)
+    gj = None
+    if grad_cost is not None:
+        gj = mem.contig(grad_cost, "f64")
+        if math.prod(gj.shape) != ci.B:
+            raise ValueError("grad_cost must hold %d elements (one per trajectory)" % ci.B)
+    desc = ci.desc(order, False, 0.0, vel_zero_weight)
+    gwp = mem.empty(ci.waypoints.shape, ci.io) if "waypoints" in want else None
+    gtm = mem.empty(ci.times.shape, ci.io) if "times" in want else None
+    gkv = mem.empty(kv.shape, ci.io) if "knot_values" in want else None
+    stt = mem.empty((ci.B,), "i32") if want_status else None
+    wsp, need = _workspace(mem, workspace, knots_vjp_workspace_bytes, desc, gco is not None)
+    _check(_lib.csp_minsnap_solve_knots_batch_vjp(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(mk), p(kv), p(gco), p(gj),
+                                                  p(gwp), p(gtm), p(gkv), p(stt), wsp, need, mem.stream(stream)))
+    return KnotsVjpResult(gwp, gtm, gkv, stt)
+
+
+def _make_knots_autograd_fn():
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class SolveKnotsFn(torch.autograd.Function):
+        """(coeffs, cost) = solve_knots_batch(waypoints, times, knot_mask, knot_values); backward = one
+        solve_knots_batch_vjp for the inputs that need it."""
+
+        @staticmethod
+        def forward(ctx, waypoints, times, knot_values, knot_mask, order, vel_zero_weight, seg_offsets, max_segments,
+                    vel_zero_weight_per_traj, with_cost):
+            r = solve_knots_batch(waypoints.detach(), times.detach(), knot_mask, knot_values.detach(), order=order,
+                                  vel_zero_weight=vel_zero_weight, seg_offsets=seg_offsets, max_segments=max_segments,
+                                  vel_zero_weight_per_traj=vel_zero_weight_per_traj, want_cost=with_cost)
+            ctx.save_for_backward(waypoints, times, knot_values, seg_offsets, vel_zero_weight_per_traj)
+            ctx.knot_mask = knot_mask
+            ctx.order, ctx.vel_zero_weight, ctx.max_segments = order, vel_zero_weight, max_segments
+            ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None, not as zeros
+            return (r.coeffs, r.cost) if with_cost else r.coeffs
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_coeffs, grad_cost=None):
+            waypoints, times, knot_values, seg_offsets, vwp = ctx.saved_tensors
+            needs = ctx.needs_input_grad[:3]
+            want = tuple(n for n, f in zip(_KNOTS_VJP_WANT, needs) if f)
+            if not want or (grad_coeffs is None and grad_cost is None):
+                return (None,) * 10
+            g = solve_knots_batch_vjp(waypoints, times, ctx.knot_mask, knot_values, grad_coeffs=grad_coeffs,
+                                      grad_cost=grad_cost, order=ctx.order, vel_zero_weight=ctx.vel_zero_weight,
+                                      seg_offsets=seg_offsets, max_segments=ctx.max_segments, vel_zero_weight_per_traj=vwp,
+                                      want=want)
+            gwp = g.waypoints.to(waypoints.dtype).reshape(waypoints.shape) if needs[0] else None
+            gtm = g.times.to(times.dtype).reshape(times.shape) if needs[1] else None
+            gkv = g.knot_values.to(knot_values.dtype).reshape(knot_values.shape) if needs[2] else None
+            return (gwp, gtm, gkv) + (None,) * 7
+
+    return SolveKnotsFn
+
+
+_knots_autograd_fn = None
+
+
+def solve_knots_batch_autograd(waypoints, times, knot_mask, knot_values, order=4, vel_zero_weight=0.0, seg_offsets=None,
+                               max_segments=None, vel_zero_weight_per_traj=None, with_cost=False):
+    """solve_knots_batch as a differentiable torch op (CUDA tensors; knot_mask may be a numpy array): returns the
+    coefficients, or (coeffs, cost) with `with_cost` -- bit-equal to solve_knots_batch(...) -- with a grad_fn when
+    waypoints, times or knot_values require grad.  The backward pass is one csp_minsnap_solve_knots_batch_vjp for the
+    inputs that need a gradient; grad_coeffs or grad_cost is passed only when that output received a cotangent, so a loss
+    on the cost alone runs the three-column kernel.  The gradient of a value whose mask bit is clear is 0.  First-order
+    only (once_differentiable); no gradient with respect to the mask or the weights."""
+    global _knots_autograd_fn
+    if _knots_autograd_fn is None:
+        _knots_autograd_fn = _make_knots_autograd_fn()
+    if isinstance(knot_values, np.ndarray):
+        knot_values = torch.from_numpy(np.ascontiguousarray(knot_values)).to(device=waypoints.device, dtype=waypoints.dtype)
+    return _knots_autograd_fn.apply(waypoints, times, knot_values, knot_mask, order, vel_zero_weight, seg_offsets,
+                                    max_segments, vel_zero_weight_per_traj, with_cost)
 
 
 def _make_periodic_autograd_fn():

@@ -10,6 +10,7 @@
 #include "minsnap_eval.h"
 #include "minsnap_periodic_vjp.h"
 #include "minsnap_knots.h"
+#include "minsnap_knots_vjp.h"
 #include "minsnap_vjp.h"
 #include "minsnap_hoststage.h"
 #include "minsnap_timealloc.h"
@@ -727,6 +728,27 @@ int dispatch_knots(const csp_minsnap_desc *d, const Shape &s, const void *wp, co
     a.B = s.B; a.S = s.S; a.Smax = s.Smax; a.order = s.order;
     hipError_t e = csp::launch_knots(a, s.f32, st);
     if (e != hipSuccess) return hip_fail(e, "knots kernel launch");
+    return CSP_OK;
+}
+
+// csp_minsnap_solve_knots_batch_vjp: the knots solve's scope and layouts.  Knots 0..Smax of every trajectory, six
+// right-hand-side columns under a grad_coeffs cotangent (pbar), three without.
+size_t knots_vjp_ws_bytes(const Shape &s, bool pbar) {
+    return align_up((size_t)(s.Smax + 1) * csp::knots_vjp_ws_entries(s.order, pbar) * (size_t)s.B * 8, 256);
+}
+
+int dispatch_knots_vjp(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const uint8_t *mask,
+                       const void *values, const void *gco, const double *gcost, void *gwp, void *gtm, void *gkv,
+                       int32_t *status, const int64_t *seg_off, const double *vw_per, void *ws, hipStream_t st) {
+    csp::KnotsVjpArgs a{};
+    a.wp = wp; a.times = tm; a.mask = mask; a.values = values; a.grad_coeffs = gco; a.grad_cost = gcost;
+    a.grad_wp = gwp; a.grad_times = gtm; a.grad_values = gkv; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.ws = ws; a.vw_per = vw_per;
+    a.vel_zero_weight = d->vel_zero_weight;
+    a.B = s.B; a.S = s.S; a.Smax = s.Smax; a.order = s.order;
+    hipError_t e = csp::launch_knots_vjp(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, "knots vjp kernel launch");
     return CSP_OK;
 }
 
@@ -1773,6 +1795,55 @@ int csp_minsnap_solve_knots_batch(const csp_minsnap_desc *desc, const void *wayp
         return dispatch_knots(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr<const uint8_t>(o_mk), g.ptr(o_kv), g.ptr(o_co),
                               g.ptr<double>(o_c), g.ptr<int32_t>(o_st), g.ptr<const int64_t>(g.seg_off),
                               g.ptr<const double>(g.vw_per), g.ptr(o_ws), st);
+    });
+}
+
+size_t csp_minsnap_knots_vjp_workspace_bytes(const csp_minsnap_desc *desc, int with_grad_coeffs) {
+    Shape s;
+    if (validate_vjp(desc, s) != CSP_OK) return 0;
+    return knots_vjp_ws_bytes(s, with_grad_coeffs != 0);
+}
+
+int csp_minsnap_solve_knots_batch_vjp(const csp_minsnap_desc *desc, const void *waypoints, const void *times,
+                                      const uint8_t *knot_mask, const void *knot_values, const void *grad_coeffs,
+                                      const double *grad_cost, void *grad_waypoints, void *grad_times,
+                                      void *grad_knot_values, int32_t *status, void *workspace, size_t workspace_bytes,
+                                      void *hip_stream) {
+    Shape s;
+    int rc = validate_vjp(desc, s);
+    if (rc != CSP_OK) return rc;
+    if (s.B == 0) return CSP_OK;
+    if (!waypoints || !times || !knot_mask || !knot_values) return CSP_ERR_INVALID_ARG;
+    if (!grad_coeffs && !grad_cost) return CSP_ERR_INVALID_ARG;
+    if (!grad_waypoints && !grad_times && !grad_knot_values) return CSP_ERR_INVALID_ARG;
+    const size_t n_ws = knots_vjp_ws_bytes(s, grad_coeffs != nullptr);
+    if (desc->mem_space == CSP_MEM_DEVICE) {
+        if (!workspace || workspace_bytes < n_ws) return CSP_ERR_WORKSPACE;
+        if ((uintptr_t)workspace & 7u) return CSP_ERR_WORKSPACE;
+        if ((uintptr_t)grad_coeffs & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // p_bar records are read as 2-element vectors
+    } else if (!offsets_ok(desc, s)) {
+        return CSP_ERR_INVALID_ARG;
+    }
+    rc = select_device(desc->device_id);
+    if (rc != CSP_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+
+    if (desc->mem_space == CSP_MEM_DEVICE)
+        return dispatch_knots_vjp(desc, s, waypoints, times, knot_mask, knot_values, grad_coeffs, grad_cost, grad_waypoints,
+                                  grad_times, grad_knot_values, status, desc->seg_offsets, desc->vel_zero_weight_per_traj,
+                                  workspace, st);
+
+    // CSP_MEM_HOST: as csp_minsnap_solve_knots_batch
+    Stage g(desc, s, st, waypoints, times, nullptr, false);
+    const size_t n_knots = (size_t)(g.z.total_seg + s.B), n_kv = n_knots * (size_t)(s.order - 1) * 3 * s.elt;
+    const size_t o_mk = g.in(knot_mask, n_knots), o_kv = g.in(knot_values, n_kv);
+    const size_t o_gc = g.in(grad_coeffs, g.z.co), o_gj = g.in(grad_cost, (size_t)s.B * 8);
+    const size_t o_gw = g.out(grad_waypoints, g.z.wp), o_gt = g.out(grad_times, g.z.tm), o_gk = g.out(grad_knot_values, n_kv);
+    const size_t o_st = g.out(status, (size_t)s.B * 4), o_ws = g.hc.scratch(n_ws);
+    return g.run([&] {
+        return dispatch_knots_vjp(desc, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr<const uint8_t>(o_mk), g.ptr(o_kv), g.ptr(o_gc),
+                                  g.ptr<const double>(o_gj), g.ptr(o_gw), g.ptr(o_gt), g.ptr(o_gk), g.ptr<int32_t>(o_st),
+                                  g.ptr<const int64_t>(g.seg_off), g.ptr<const double>(g.vw_per), g.ptr(o_ws), st);
     });
 }
 

@@ -391,6 +391,49 @@ int csp_minsnap_solve_knots_batch(const csp_minsnap_desc *desc, const void *wayp
 /* Device scratch bytes csp_minsnap_solve_knots_batch needs (formula above; 0 for an invalid or unsupported descriptor). */
 size_t csp_minsnap_knots_workspace_bytes(const csp_minsnap_desc *desc);
 
+/* Reverse mode of csp_minsnap_solve_knots_batch: given grad_coeffs = dL/dcoeffs and / or grad_cost =
+ * dL/dcost for a scalar L of that call's coefficients and cost, writes dL/dwaypoints, dL/dtimes and dL/dknot_values.  The
+ * adjoint system is the forward's masked block-tridiagonal matrix, shared by the three axes; the primal is re-solved
+ * from the inputs in the same sweep (the forward's coefficients are not an input).  One lane per trajectory, every
+ * output written once by its owner, no atomics: two calls give identical bits, and an output's bits do not depend on
+ * which other outputs are asked for.  There is no gradient for the mask or the weights.
+ *   desc             : the scope, layouts (RAGGED LAYOUT included) and CSP_ERR_UNSUPPORTED cases of
+ *                      csp_minsnap_solve_knots_batch; bc_per_trajectory is ignored
+ *   waypoints, times, knot_mask, knot_values : the forward's inputs (a value whose mask bit is clear is never used, mask
+ *                      bits from order-1 upward are ignored)
+ *   grad_coeffs      : optional, [B][S][3][2*order], the layout and storage type of coeffs; 16-byte aligned (fp64) /
+ *                      8-byte (fp32) for a device call.  NULL: its terms are not computed, the adjoint columns are not run
+ *                      and the workspace is the smaller one
+ *   grad_cost        : optional, [B] f64; NULL means 0 (its terms are then not computed).  CSP_ERR_INVALID_ARG when both
+ *                      cotangents are NULL.
+ *   grad_waypoints   : optional out, the layout and storage type of `waypoints`
+ *   grad_times       : optional out, the layout and storage type of `times`
+ *   grad_knot_values : optional out, the layout and storage type of `knot_values`.  The entry of a slot whose mask bit is
+ *                      clear is exactly 0.0, whatever knot_values holds there.  CSP_ERR_INVALID_ARG when all three outputs
+ *                      are NULL.
+ *   status           : optional out, [B] i32, the forward's rules in the forward's order.  S_b = 0: status 0, zeros in the
+ *                      trajectory's one knot row of grad_waypoints and grad_knot_values.  A ragged trajectory longer than
+ *                      max_segments (CSP_MEM_DEVICE; CSP_MEM_HOST: CSP_ERR_INVALID_ARG): CSP_TRAJ_SKIPPED, every gradient
+ *                      row it owns is NaN, the workspace is not touched for it.  A constraint count below the order:
+ *                      CSP_TRAJ_NOT_SPD, decided before the sweep, every gradient row it owns is NaN.  A segment time that
+ *                      is not > 0 or a pivot <= 0: CSP_TRAJ_NOT_SPD.  A written gradient that is inf/NaN:
+ *                      CSP_TRAJ_NONFINITE.  A bad trajectory does not change any output of another one.
+ *   workspace        : device scratch of csp_minsnap_knots_vjp_workspace_bytes(desc, grad_coeffs != NULL) bytes
+ *                      (CSP_MEM_DEVICE, 8-byte aligned); may be NULL/0 with CSP_MEM_HOST.  With o = order, Smax =
+ *                      num_segments (uniform) or max_segments (ragged), c = 6 with grad_coeffs and 3 without:
+ *                        round_up_256((Smax + 1) * ((o-1)^2 + c(o-1)) * B * 8)
+ * Arguments (NULL inputs, both cotangents or all outputs NULL, workspace size and alignment, the alignment of grad_coeffs
+ * of a device call, ragged host offsets outside 0..max_segments) are checked before a device is looked for.
+ * CSP_MEM_HOST: staged through the cached arena, synchronous.  CSP_MEM_DEVICE: asynchronous on `hip_stream`. */
+int csp_minsnap_solve_knots_batch_vjp(const csp_minsnap_desc *desc, const void *waypoints, const void *times,
+                                      const uint8_t *knot_mask, const void *knot_values, const void *grad_coeffs,
+                                      const double *grad_cost, void *grad_waypoints, void *grad_times,
+                                      void *grad_knot_values, int32_t *status, void *workspace, size_t workspace_bytes,
+                                      void *hip_stream);
+/* Device scratch bytes csp_minsnap_solve_knots_batch_vjp needs (formula above; 0 for an invalid or unsupported
+ * descriptor). */
+size_t csp_minsnap_knots_vjp_workspace_bytes(const csp_minsnap_desc *desc, int with_grad_coeffs);
+
 /* The same solve spread over `ngpu` devices of this node from ONE process (the reference planner
  * is a single C++ process).  Trajectories are independent
  * (minimum_snap.cpp has no cross-trajectory term), so the batch is cut into `ngpu` contiguous shards, shard g on the
