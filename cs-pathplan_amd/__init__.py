@@ -403,6 +403,35 @@ class _CallInputs:
         return (self.S, self.B, 3, m) if segment_major else (self.B, self.S, 3, m)
 
 
+def _cotangents(ci, grad_coeffs, grad_cost, order):
+    """(grad_coeffs in the storage dtype, grad_cost as f64) of a reverse-mode call on `ci`, contiguous and checked against
+    its sizes.  One that is None stays None: which of the two may be is the entry's choice."""
+    mem = ci.mem
+    gco = gj = None
+    if grad_coeffs is not None:
+        gco = mem.contig(grad_coeffs, ci.io)
+        if mem.mem_space == MEM_DEVICE and gco.data_ptr() % 16:   # the kernel reads it in 16-byte pieces (host memory is staged)
+            gco = gco.clone()
+        n = ci.total * 3 * 2 * int(order)
+        if math.prod(gco.shape) != n:
+            raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % n)
+    if grad_cost is not None:
+        gj = mem.contig(grad_cost, "f64")
+        if math.prod(gj.shape) != ci.B:
+            raise ValueError("grad_cost must hold %d elements (one per trajectory)" % ci.B)
+    return gco, gj
+
+
+def _wanted(mem, want, names, like, kind):
+    """Checks `want` against the family's `names`; then one uninitialised gradient array per name, in the family's order
+    and shaped as the input in `like`, None where the name is not wanted."""
+    want = tuple(want)
+    for w in want:
+        if w not in names:
+            raise ValueError("want: a subset of %r" % (names,))
+    return [mem.empty(x.shape, kind) if name in want else None for name, x in zip(names, like)]
+
+
 class Result:
     __slots__ = ("coeffs", "max_dev", "status", "kernel")
 
@@ -475,31 +504,14 @@ def solve_batch_vjp(waypoints, times, grad_coeffs, bc=None, order=4, vel_zero_we
     grad_cost = dL/dcost [B] (the cost of snap_cost_batch at the same inputs) adds the cost's cotangent
     (csp_minsnap_solve_batch_cost_vjp); grad_coeffs may then be None: the cost-only kernel, which needs
     no adjoint solve and reads no coefficient cotangent."""
-    want = tuple(want)
-    for w in want:
-        if w not in _VJP_WANT:
-            raise ValueError("want: a subset of %r" % (_VJP_WANT,))
     ci = _CallInputs(waypoints, times, bc, seg_offsets, max_segments, vel_zero_weight_per_traj)
     mem, p = ci.mem, ci.mem.ptr
-    gco = gj = None
-    if grad_coeffs is not None:
-        gco = mem.contig(grad_coeffs, ci.io)
-        if mem.mem_space == MEM_DEVICE and gco.data_ptr() % 16:   # the kernel reads it in 16-byte pieces (host memory is staged)
-            gco = gco.clone()
-        n = ci.total * 3 * 2 * int(order)
-        if math.prod(gco.shape) != n:
-            raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % n)
-    elif grad_cost is None:
+    if grad_coeffs is None and grad_cost is None:
         raise ValueError("grad_coeffs may be None only with a grad_cost")
-    if grad_cost is not None:
-        gj = mem.contig(grad_cost, "f64")
-        if math.prod(gj.shape) != ci.B:
-            raise ValueError("grad_cost must hold %d elements (one per trajectory)" % ci.B)
+    gco, gj = _cotangents(ci, grad_coeffs, grad_cost, order)
     # B == 1 counts as per trajectory here: the library sizes the workspace and picks the bc reduction from this flag
     desc = ci.desc(order, ci.checked_bc_per_trajectory(), 0.0, vel_zero_weight)
-    gwp = mem.empty(ci.waypoints.shape, ci.io) if "waypoints" in want else None
-    gtm = mem.empty(ci.times.shape, ci.io) if "times" in want else None
-    gbc = mem.empty(ci.bc.shape, ci.io) if "bc" in want else None
+    gwp, gtm, gbc = _wanted(mem, want, _VJP_WANT, (ci.waypoints, ci.times, ci.bc), ci.io)
     stt = mem.empty((ci.B,), "i32") if want_status else None
     if gj is None:
         wsp, need = _workspace(mem, workspace, vjp_workspace_bytes, desc)
@@ -512,49 +524,56 @@ def solve_batch_vjp(waypoints, times, grad_coeffs, bc=None, order=4, vel_zero_we
     return VjpResult(gwp, gtm, gbc, stt)
 
 
-def _make_autograd_fn():
-    import torch
+_autograd_fns = {}
+
+
+def _autograd_fn(names, forward, vjp):
+    """The torch.autograd.Function of one family, built at first use.  apply() takes the family's differentiable inputs
+    (`names`, in the order of its VJP's `want`), then whatever else `forward` and `vjp` take.  forward(*args) returns
+    the outputs; backward makes one call, vjp(want, grad_coeffs, grad_cost, *args), for the inputs that need a gradient,
+    and hands each back in its input's shape and dtype."""
+    if forward in _autograd_fns:
+        return _autograd_fns[forward]
     from torch.autograd.function import once_differentiable
+    n = len(names)
 
-    class SolveBatchFn(torch.autograd.Function):
-        """coeffs (or coeffs, cost) = solve_batch (and snap_cost_batch) of (waypoints, times, bc); backward = one
-        solve_batch_vjp for the inputs that need it."""
-
+    class Fn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj,
-                    with_cost):
-            kw = dict(order=order, vel_zero_weight=vel_zero_weight, seg_offsets=seg_offsets, max_segments=max_segments,
-                      vel_zero_weight_per_traj=vel_zero_weight_per_traj)
-            wp, tm, bcd = waypoints.detach(), times.detach(), None if bc is None else bc.detach()
-            r = solve_batch(wp, tm, bcd, **kw)
-            ctx.save_for_backward(waypoints, times, bc, seg_offsets, vel_zero_weight_per_traj)
-            ctx.order, ctx.vel_zero_weight, ctx.max_segments = order, vel_zero_weight, max_segments
-            if not with_cost:
-                return r.coeffs
+        def forward(ctx, *args):
+            ctx.save_for_backward(*args[:n])
+            ctx.rest = args[n:]
             ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None, not as zeros
-            return r.coeffs, snap_cost_batch(wp, tm, bcd, want_grad=False, **kw).cost
+            return forward(*(x if x is None else x.detach() for x in args[:n]), *args[n:])
 
         @staticmethod
         @once_differentiable
         def backward(ctx, grad_coeffs, grad_cost=None):
-            waypoints, times, bc, seg_offsets, vwp = ctx.saved_tensors
-            need_wp, need_tm, need_bc = ctx.needs_input_grad[:3]
-            want = tuple(n for n, f in zip(_VJP_WANT, (need_wp, need_tm, need_bc)) if f)
+            xs, needs = ctx.saved_tensors, ctx.needs_input_grad[:n]
+            want = tuple(k for k, f in zip(names, needs) if f)
             if not want or (grad_coeffs is None and grad_cost is None):
-                return (None,) * 9
-            kw = {} if grad_cost is None else {"grad_cost": grad_cost}   # the cost alone: grad_coeffs stays None
-            g = solve_batch_vjp(waypoints, times, grad_coeffs, bc=bc, order=ctx.order, vel_zero_weight=ctx.vel_zero_weight,
-                                seg_offsets=seg_offsets, max_segments=ctx.max_segments, vel_zero_weight_per_traj=vwp,
-                                want=want, **kw)
-            gwp = g.waypoints.to(waypoints.dtype) if need_wp else None
-            gtm = g.times.to(times.dtype) if need_tm else None
-            gbc = g.bc.reshape(bc.shape).to(bc.dtype) if need_bc else None
-            return gwp, gtm, gbc, None, None, None, None, None, None
+                return (None,) * (n + len(ctx.rest))
+            g = vjp(want, grad_coeffs, grad_cost, *xs, *ctx.rest)
+            return tuple(getattr(g, k).reshape(x.shape).to(x.dtype) if f else None
+                         for k, x, f in zip(names, xs, needs)) + (None,) * len(ctx.rest)
 
-    return SolveBatchFn
+    _autograd_fns[forward] = Fn
+    return Fn
 
 
-_autograd_fn = None
+def _solve_kw(order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj):
+    """The keywords every solve family's forward and VJP take alike."""
+    return dict(order=order, vel_zero_weight=vel_zero_weight, seg_offsets=seg_offsets, max_segments=max_segments,
+                vel_zero_weight_per_traj=vel_zero_weight_per_traj)
+
+
+def _solve_forward(wp, tm, bc, with_cost, kw):
+    r = solve_batch(wp, tm, bc, **kw)
+    return (r.coeffs, snap_cost_batch(wp, tm, bc, want_grad=False, **kw).cost) if with_cost else r.coeffs
+
+
+def _solve_vjp(want, grad_coeffs, grad_cost, wp, tm, bc, with_cost, kw):
+    ckw = {} if grad_cost is None else {"grad_cost": grad_cost}   # the cost alone: grad_coeffs stays None
+    return solve_batch_vjp(wp, tm, grad_coeffs, bc=bc, want=want, **kw, **ckw)
 
 
 def solve_batch_autograd(waypoints, times, bc=None, order=4, vel_zero_weight=0.0, seg_offsets=None, max_segments=None,
@@ -566,11 +585,8 @@ def solve_batch_autograd(waypoints, times, bc=None, order=4, vel_zero_weight=0.0
     with_cost: returns (coeffs, cost), the cost bit-equal to snap_cost_batch(...).cost.  The backward pass is then one
     csp_minsnap_solve_batch_cost_vjp with the cotangents that arrived; a loss on the cost alone runs the cost-only
     kernel (no adjoint solve, no zero coefficient cotangent is allocated)."""
-    global _autograd_fn
-    if _autograd_fn is None:
-        _autograd_fn = _make_autograd_fn()
-    return _autograd_fn.apply(waypoints, times, bc, order, vel_zero_weight, seg_offsets, max_segments,
-                              vel_zero_weight_per_traj, with_cost)
+    kw = _solve_kw(order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    return _autograd_fn(_VJP_WANT, _solve_forward, _solve_vjp).apply(waypoints, times, bc, with_cost, kw)
 
 
 def cost_workspace_bytes(desc):
@@ -699,26 +715,11 @@ def solve_periodic_batch_vjp(waypoints, times, grad_coeffs, grad_cost=None, orde
     grad_coeffs = dL/dcoeffs in the layout of that call's coefficients and, optionally, grad_cost = dL/dcost [B], returns
     PeriodicVjpResult(dL/dwaypoints, dL/dtimes, status) for the names in `want`.  Inputs as in solve_periodic_batch:
     numpy arrays -> CSP_MEM_HOST, torch CUDA tensors -> CSP_MEM_DEVICE."""
-    want = tuple(want)
-    for w in want:
-        if w not in _PERIODIC_VJP_WANT:
-            raise ValueError("want: a subset of %r" % (_PERIODIC_VJP_WANT,))
     ci = _CallInputs(waypoints, times, None, seg_offsets, max_segments, vel_zero_weight_per_traj)
     mem, p = ci.mem, ci.mem.ptr
-    gco = mem.contig(grad_coeffs, ci.io)
-    if mem.mem_space == MEM_DEVICE and gco.data_ptr() % 16:   # the kernel reads it in 16-byte pieces (host memory is staged)
-        gco = gco.clone()
-    n = ci.total * 3 * 2 * int(order)
-    if math.prod(gco.shape) != n:
-        raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % n)
-    gj = None
-    if grad_cost is not None:
-        gj = mem.contig(grad_cost, "f64")
-        if math.prod(gj.shape) != ci.B:
-            raise ValueError("grad_cost must hold %d elements (one per trajectory)" % ci.B)
+    gco, gj = _cotangents(ci, grad_coeffs, grad_cost, order)   # (the library refuses a null grad_coeffs)
     desc = ci.desc(order, ci.checked_bc_per_trajectory(), 0.0, vel_zero_weight)
-    gwp = mem.empty(ci.waypoints.shape, ci.io) if "waypoints" in want else None
-    gtm = mem.empty(ci.times.shape, ci.io) if "times" in want else None
+    gwp, gtm = _wanted(mem, want, _PERIODIC_VJP_WANT, (ci.waypoints, ci.times), ci.io)
     stt = mem.empty((ci.B,), "i32") if want_status else None
     wsp, need = _workspace(mem, workspace, periodic_vjp_workspace_bytes, desc)
     _check(_lib.csp_minsnap_solve_periodic_batch_vjp(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(gco), p(gj), p(gwp),
@@ -833,32 +834,14 @@ def solve_knots_batch_vjp(waypoints, times, knot_mask, knot_values, grad_coeffs=
     0.0 at every slot whose mask bit is clear.  Without grad_coeffs the three-column kernel runs and grad_coeffs is never
     allocated or read.  Inputs as in solve_knots_batch: numpy arrays -> CSP_MEM_HOST, torch CUDA tensors ->
     CSP_MEM_DEVICE (knot_mask and knot_values may be numpy arrays beside device waypoints)."""
-    want = tuple(want)
-    for w in want:
-        if w not in _KNOTS_VJP_WANT:
-            raise ValueError("want: a subset of %r" % (_KNOTS_VJP_WANT,))
     if grad_coeffs is None and grad_cost is None:
         raise ValueError("solve_knots_batch_vjp needs grad_coeffs, grad_cost or both")
     ci = _CallInputs(waypoints, times, None, seg_offsets, max_segments, vel_zero_weight_per_traj)
     mem, p = ci.mem, ci.mem.ptr
     mk, kv = _knot_arrays(ci, knot_mask, knot_values, order)
-    gco = None
-    if grad_coeffs is not None:
-        gco = mem.contig(grad_coeffs, ci.io)
-        if mem.mem_space == MEM_DEVICE and gco.data_ptr() % 16:   # the kernel reads it in 16-byte pieces (host memory is staged)
-            gco = gco.clone()
-        n = ci.total * 3 * 2 * int(order)
-        if math.prod(gco.shape) != n:
-            raise ValueError("grad_coeffs must hold %d elements (the coefficients' layout)" % n)
-    gj = None
-    if grad_cost is not None:
-        gj = mem.contig(grad_cost, "f64")
-        if math.prod(gj.shape) != ci.B:
-            raise ValueError("grad_cost must hold %d elements (one per trajectory)" % ci.B)
+    gco, gj = _cotangents(ci, grad_coeffs, grad_cost, order)
     desc = ci.desc(order, False, 0.0, vel_zero_weight)
-    gwp = mem.empty(ci.waypoints.shape, ci.io) if "waypoints" in want else None
-    gtm = mem.empty(ci.times.shape, ci.io) if "times" in want else None
-    gkv = mem.empty(kv.shape, ci.io) if "knot_values" in want else None
+    gwp, gtm, gkv = _wanted(mem, want, _KNOTS_VJP_WANT, (ci.waypoints, ci.times, kv), ci.io)
     stt = mem.empty((ci.B,), "i32") if want_status else None
     wsp, need = _workspace(mem, workspace, knots_vjp_workspace_bytes, desc, gco is not None)
     _check(_lib.csp_minsnap_solve_knots_batch_vjp(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(mk), p(kv), p(gco), p(gj),
@@ -866,47 +849,13 @@ def solve_knots_batch_vjp(waypoints, times, knot_mask, knot_values, grad_coeffs=
     return KnotsVjpResult(gwp, gtm, gkv, stt)
 
 
-def _make_knots_autograd_fn():
-    import torch
-    from torch.autograd.function import once_differentiable
-
-    class SolveKnotsFn(torch.autograd.Function):
-        """(coeffs, cost) = solve_knots_batch(waypoints, times, knot_mask, knot_values); backward = one
-        solve_knots_batch_vjp for the inputs that need it."""
-
-        @staticmethod
-        def forward(ctx, waypoints, times, knot_values, knot_mask, order, vel_zero_weight, seg_offsets, max_segments,
-                    vel_zero_weight_per_traj, with_cost):
-            r = solve_knots_batch(waypoints.detach(), times.detach(), knot_mask, knot_values.detach(), order=order,
-                                  vel_zero_weight=vel_zero_weight, seg_offsets=seg_offsets, max_segments=max_segments,
-                                  vel_zero_weight_per_traj=vel_zero_weight_per_traj, want_cost=with_cost)
-            ctx.save_for_backward(waypoints, times, knot_values, seg_offsets, vel_zero_weight_per_traj)
-            ctx.knot_mask = knot_mask
-            ctx.order, ctx.vel_zero_weight, ctx.max_segments = order, vel_zero_weight, max_segments
-            ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None, not as zeros
-            return (r.coeffs, r.cost) if with_cost else r.coeffs
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, grad_coeffs, grad_cost=None):
-            waypoints, times, knot_values, seg_offsets, vwp = ctx.saved_tensors
-            needs = ctx.needs_input_grad[:3]
-            want = tuple(n for n, f in zip(_KNOTS_VJP_WANT, needs) if f)
-            if not want or (grad_coeffs is None and grad_cost is None):
-                return (None,) * 10
-            g = solve_knots_batch_vjp(waypoints, times, ctx.knot_mask, knot_values, grad_coeffs=grad_coeffs,
-                                      grad_cost=grad_cost, order=ctx.order, vel_zero_weight=ctx.vel_zero_weight,
-                                      seg_offsets=seg_offsets, max_segments=ctx.max_segments, vel_zero_weight_per_traj=vwp,
-                                      want=want)
-            gwp = g.waypoints.to(waypoints.dtype).reshape(waypoints.shape) if needs[0] else None
-            gtm = g.times.to(times.dtype).reshape(times.shape) if needs[1] else None
-            gkv = g.knot_values.to(knot_values.dtype).reshape(knot_values.shape) if needs[2] else None
-            return (gwp, gtm, gkv) + (None,) * 7
-
-    return SolveKnotsFn
+def _knots_forward(wp, tm, kv, knot_mask, with_cost, kw):
+    r = solve_knots_batch(wp, tm, knot_mask, kv, want_cost=with_cost, **kw)
+    return (r.coeffs, r.cost) if with_cost else r.coeffs
 
 
-_knots_autograd_fn = None
+def _knots_vjp(want, grad_coeffs, grad_cost, wp, tm, kv, knot_mask, with_cost, kw):
+    return solve_knots_batch_vjp(wp, tm, knot_mask, kv, grad_coeffs=grad_coeffs, grad_cost=grad_cost, want=want, **kw)
 
 
 def solve_knots_batch_autograd(waypoints, times, knot_mask, knot_values, order=4, vel_zero_weight=0.0, seg_offsets=None,
@@ -917,55 +866,22 @@ def solve_knots_batch_autograd(waypoints, times, knot_mask, knot_values, order=4
     inputs that need a gradient; grad_coeffs or grad_cost is passed only when that output received a cotangent, so a loss
     on the cost alone runs the three-column kernel.  The gradient of a value whose mask bit is clear is 0.  First-order
     only (once_differentiable); no gradient with respect to the mask or the weights."""
-    global _knots_autograd_fn
-    if _knots_autograd_fn is None:
-        _knots_autograd_fn = _make_knots_autograd_fn()
     if isinstance(knot_values, np.ndarray):
         knot_values = torch.from_numpy(np.ascontiguousarray(knot_values)).to(device=waypoints.device, dtype=waypoints.dtype)
-    return _knots_autograd_fn.apply(waypoints, times, knot_values, knot_mask, order, vel_zero_weight, seg_offsets,
-                                    max_segments, vel_zero_weight_per_traj, with_cost)
+    kw = _solve_kw(order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    fn = _autograd_fn(_KNOTS_VJP_WANT, _knots_forward, _knots_vjp)
+    return fn.apply(waypoints, times, knot_values, knot_mask, with_cost, kw)
 
 
-def _make_periodic_autograd_fn():
-    import torch
-    from torch.autograd.function import once_differentiable
-
-    class SolvePeriodicFn(torch.autograd.Function):
-        """(coeffs, cost) = solve_periodic_batch(waypoints, times); backward = solve_periodic_batch_vjp for the inputs
-        that need it."""
-
-        @staticmethod
-        def forward(ctx, waypoints, times, order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj,
-                    with_cost):
-            r = solve_periodic_batch(waypoints.detach(), times.detach(), order=order, vel_zero_weight=vel_zero_weight,
-                                     seg_offsets=seg_offsets, max_segments=max_segments,
-                                     vel_zero_weight_per_traj=vel_zero_weight_per_traj, want_cost=with_cost)
-            ctx.save_for_backward(waypoints, times, seg_offsets, vel_zero_weight_per_traj)
-            ctx.order, ctx.vel_zero_weight, ctx.max_segments = order, vel_zero_weight, max_segments
-            ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None, not as zeros
-            return (r.coeffs, r.cost) if with_cost else r.coeffs
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, grad_coeffs, grad_cost=None):
-            waypoints, times, seg_offsets, vwp = ctx.saved_tensors
-            need_wp, need_tm = ctx.needs_input_grad[:2]
-            want = tuple(n for n, f in zip(_PERIODIC_VJP_WANT, (need_wp, need_tm)) if f)
-            if not want or (grad_coeffs is None and grad_cost is None):
-                return (None,) * 8
-            if grad_coeffs is None:   # the loss uses the cost alone
-                grad_coeffs = times.new_zeros((math.prod(times.shape), 3, 2 * ctx.order))
-            g = solve_periodic_batch_vjp(waypoints, times, grad_coeffs, grad_cost=grad_cost, order=ctx.order,
-                                         vel_zero_weight=ctx.vel_zero_weight, seg_offsets=seg_offsets,
-                                         max_segments=ctx.max_segments, vel_zero_weight_per_traj=vwp, want=want)
-            gwp = g.waypoints.to(waypoints.dtype) if need_wp else None
-            gtm = g.times.to(times.dtype) if need_tm else None
-            return gwp, gtm, None, None, None, None, None, None
-
-    return SolvePeriodicFn
+def _periodic_forward(wp, tm, with_cost, kw):
+    r = solve_periodic_batch(wp, tm, want_cost=with_cost, **kw)
+    return (r.coeffs, r.cost) if with_cost else r.coeffs
 
 
-_periodic_autograd_fn = None
+def _periodic_vjp(want, grad_coeffs, grad_cost, wp, tm, with_cost, kw):
+    if grad_coeffs is None:   # the loss uses the cost alone
+        grad_coeffs = tm.new_zeros((math.prod(tm.shape), 3, 2 * kw["order"]))
+    return solve_periodic_batch_vjp(wp, tm, grad_coeffs, grad_cost=grad_cost, want=want, **kw)
 
 
 def solve_periodic_batch_autograd(waypoints, times, order=4, vel_zero_weight=0.0, seg_offsets=None, max_segments=None,
@@ -975,11 +891,8 @@ def solve_periodic_batch_autograd(waypoints, times, order=4, vel_zero_weight=0.0
     backward pass is one csp_minsnap_solve_periodic_batch_vjp for the inputs that need a gradient; grad_cost is passed
     only when the cost received a cotangent.  First-order only (once_differentiable); no gradient with respect to the
     weights."""
-    global _periodic_autograd_fn
-    if _periodic_autograd_fn is None:
-        _periodic_autograd_fn = _make_periodic_autograd_fn()
-    return _periodic_autograd_fn.apply(waypoints, times, order, vel_zero_weight, seg_offsets, max_segments,
-                                       vel_zero_weight_per_traj, with_cost)
+    kw = _solve_kw(order, vel_zero_weight, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    return _autograd_fn(_PERIODIC_VJP_WANT, _periodic_forward, _periodic_vjp).apply(waypoints, times, with_cost, kw)
 
 
 def periodic_time_alloc_batch(waypoints, v_avg, min_time_s, seg_offsets=None):
@@ -1369,59 +1282,25 @@ def eval_batch_vjp(times, coeffs, query, grad_out, num_derivs=None, order=None, 
     taken from it unless num_derivs is given), returns EvalVjpResult(dL/dcoeffs, dL/dtimes, dL/dquery, status) for the
     names in `want`.  dL/dtimes is the explicit dependence through the local time only; the dependence of the
     coefficients on the times is solve_batch_vjp's.  Every record of dL/dcoeffs is written.  Deterministic run to run."""
-    want = tuple(want)
-    for w in want:
-        if w not in _EVAL_VJP_WANT:
-            raise ValueError("want: a subset of %r" % (_EVAL_VJP_WANT,))
     ei = _EvalInputs(times, coeffs, query, order, seg_offsets, max_segments)
     mem, p = ei.mem, ei.mem.ptr
     go = mem.contig(grad_out, ei.io)
     D = int(num_derivs) if num_derivs is not None else int(go.shape[-2])
     if math.prod(go.shape) != ei.B * ei.Q * D * 3:
         raise ValueError("grad_out must hold %d elements ([B,Q,D,3])" % (ei.B * ei.Q * D * 3))
-    gco = mem.empty(ei.coeffs.shape, ei.io) if "coeffs" in want else None
-    gtm = mem.empty(ei.times.shape, ei.io) if "times" in want else None
-    gq = mem.empty(ei.query.shape, ei.io) if "query" in want else None
+    gco, gtm, gq = _wanted(mem, want, _EVAL_VJP_WANT, (ei.coeffs, ei.times, ei.query), ei.io)
     stt = mem.zeros((ei.B,), "i32") if want_status else None
     _check(_lib.csp_minsnap_eval_batch_vjp(ctypes.byref(ei.desc), p(ei.times), p(ei.coeffs), p(ei.query), ei.Q, D, p(go), p(gco),
                                            p(gtm), p(gq), p(stt), mem.stream(stream)))
     return EvalVjpResult(gco, gtm, gq, stt)
 
 
-def _make_eval_autograd_fn():
-    import torch
-    from torch.autograd.function import once_differentiable
-
-    class EvalBatchFn(torch.autograd.Function):
-        """values = eval_batch(times, coeffs, query); backward = one eval_batch_vjp for the inputs that need it."""
-
-        @staticmethod
-        def forward(ctx, coeffs, times, query, num_derivs, seg_offsets, max_segments):
-            r = eval_batch(times.detach(), coeffs.detach(), query.detach(), num_derivs=num_derivs, seg_offsets=seg_offsets,
-                           max_segments=max_segments)
-            ctx.save_for_backward(coeffs, times, query, seg_offsets)
-            ctx.num_derivs, ctx.max_segments = num_derivs, max_segments
-            return r.values
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, grad_values):
-            coeffs, times, query, seg_offsets = ctx.saved_tensors
-            needs = ctx.needs_input_grad[:3]
-            want = tuple(n for n, f in zip(_EVAL_VJP_WANT, needs) if f)
-            if not want:
-                return (None,) * 6
-            g = eval_batch_vjp(times, coeffs, query, grad_values, num_derivs=ctx.num_derivs, seg_offsets=seg_offsets,
-                               max_segments=ctx.max_segments, want=want)
-            gco = g.coeffs.reshape(coeffs.shape).to(coeffs.dtype) if needs[0] else None
-            gtm = g.times.to(times.dtype) if needs[1] else None
-            gq = g.query.to(query.dtype) if needs[2] else None
-            return gco, gtm, gq, None, None, None
-
-    return EvalBatchFn
+def _eval_forward(co, tm, query, kw):
+    return eval_batch(tm, co, query, **kw).values
 
 
-_eval_autograd_fn = None
+def _eval_vjp(want, grad_values, _, co, tm, query, kw):
+    return eval_batch_vjp(tm, co, query, grad_values, want=want, **kw)
 
 
 def eval_batch_autograd(coeffs, times, query, num_derivs=3, seg_offsets=None, max_segments=None):
@@ -1430,10 +1309,8 @@ def eval_batch_autograd(coeffs, times, query, num_derivs=3, seg_offsets=None, ma
     csp_minsnap_eval_batch_vjp for the inputs that need a gradient; first-order only (once_differentiable).  Chains with
     solve_batch_autograd and solve_periodic_batch_autograd: pass their coefficients and the same times tensor, and
     autograd adds this op's explicit time gradient to the solve's."""
-    global _eval_autograd_fn
-    if _eval_autograd_fn is None:
-        _eval_autograd_fn = _make_eval_autograd_fn()
-    return _eval_autograd_fn.apply(coeffs, times, query, num_derivs, seg_offsets, max_segments)
+    kw = dict(num_derivs=num_derivs, seg_offsets=seg_offsets, max_segments=max_segments)
+    return _autograd_fn(_EVAL_VJP_WANT, _eval_forward, _eval_vjp).apply(coeffs, times, query, kw)
 
 
 def _geo(fn, pts, ref):

@@ -572,13 +572,20 @@ size_t vjp_ws_bytes(const csp_minsnap_desc *d, const Shape &s, bool pbar, size_t
     return factors + (d->bc_per_trajectory ? 0 : 12 * (size_t)csp::vjp_blocks(s.B) * 8);
 }
 
-// workspace and alignment of a device-memory call, from the pointers' values alone
-int check_vjp_device_args(const csp_minsnap_desc *d, const Shape &s, const void *gco, const void *ws, size_t ws_size) {
-    const size_t need = vjp_ws_bytes(d, s, gco != nullptr, nullptr);
+// Workspace and alignment of a device-memory call, from the pointers' values alone: `need` bytes of workspace at an 8-byte
+// boundary, and `rec` -- the coefficient or p_bar records, which the kernels move as 2-element vectors; null where the
+// call has none -- at one vector's.  An entry whose `need` is never 0 (knots: (Smax+1) * entries * B * 8 with B >= 1;
+// the time optimiser: 4 * Smax * B * 8 on top of the factors, Smax >= 1 and B >= 1) asks the same of a null workspace
+// with the `need > 0` guard as without it.
+int check_device_args(const Shape &s, size_t need, const void *ws, size_t ws_size, const void *rec) {
     if (need > 0 && (!ws || ws_size < need)) return CSP_ERR_WORKSPACE;
     if ((uintptr_t)ws & 7u) return CSP_ERR_WORKSPACE;
-    if ((uintptr_t)gco & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // p_bar records are read as 2-element vectors
+    if ((uintptr_t)rec & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;
     return CSP_OK;
+}
+
+int check_vjp_device_args(const csp_minsnap_desc *d, const Shape &s, const void *gco, const void *ws, size_t ws_size) {
+    return check_device_args(s, vjp_ws_bytes(d, s, gco != nullptr, nullptr), ws, ws_size, gco);
 }
 
 // gco or gcost may be null (not both): the kernel is compiled for the cotangents that are given
@@ -640,9 +647,8 @@ void timeopt_args(const csp_minsnap_desc *d, const Shape &s, csp::TimeOptArgs &a
 int dispatch_cost(const csp_minsnap_desc *d, const Shape &s, const void *wp, const void *tm, const void *bc, double *cost,
                   void *grad, int32_t *status, const int64_t *seg_off, const double *vw_per, void *ws, size_t ws_size,
                   hipStream_t st) {
-    const size_t need = cost_ws_bytes(s);
-    if (need > 0 && (!ws || ws_size < need)) return CSP_ERR_WORKSPACE;
-    if ((uintptr_t)ws & 7u) return CSP_ERR_WORKSPACE;
+    int rc = check_device_args(s, cost_ws_bytes(s), ws, ws_size, nullptr);
+    if (rc != CSP_OK) return rc;
     csp::TimeOptArgs a;
     timeopt_args(d, s, a);
     a.wp = wp; a.times = tm; a.bc = bc; a.cost = cost; a.grad = grad; a.status = status;
@@ -658,7 +664,8 @@ int dispatch_timeopt(const csp_minsnap_desc *d, const csp_minsnap_timeopt_params
                      const int64_t *seg_off, const double *vw_per, void *ws, size_t ws_size, hipStream_t st) {
     size_t vec_off = 0;
     const size_t need = timeopt_ws_bytes(s, &vec_off);
-    if (!ws || ws_size < need || ((uintptr_t)ws & 7u)) return CSP_ERR_WORKSPACE;
+    int rc = check_device_args(s, need, ws, ws_size, nullptr);
+    if (rc != CSP_OK) return rc;
     csp::TimeOptArgs a;
     timeopt_args(d, s, a);
     a.wp = wp; a.times = tm; a.bc = bc; a.times_out = tout; a.objective = obj; a.iterations = iters; a.status = status;
@@ -1688,9 +1695,8 @@ int csp_minsnap_solve_periodic_batch(const csp_minsnap_desc *desc, const void *w
     if (!waypoints || !times || !coeffs) return CSP_ERR_INVALID_ARG;
     const size_t n_ws = periodic_ws_bytes(s);
     if (desc->mem_space == CSP_MEM_DEVICE) {
-        if (n_ws > 0 && (!workspace || workspace_bytes < n_ws)) return CSP_ERR_WORKSPACE;
-        if ((uintptr_t)workspace & 7u) return CSP_ERR_WORKSPACE;
-        if ((uintptr_t)coeffs & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // records are stored as 2-element vectors
+        rc = check_device_args(s, n_ws, workspace, workspace_bytes, coeffs);
+        if (rc != CSP_OK) return rc;
     } else if (!offsets_ok(desc, s)) {
         return CSP_ERR_INVALID_ARG;
     }
@@ -1729,9 +1735,8 @@ int csp_minsnap_solve_periodic_batch_vjp(const csp_minsnap_desc *desc, const voi
     if (!waypoints || !times || !grad_coeffs || (!grad_waypoints && !grad_times)) return CSP_ERR_INVALID_ARG;
     const size_t n_ws = periodic_vjp_ws_bytes(s);
     if (desc->mem_space == CSP_MEM_DEVICE) {
-        if (n_ws > 0 && (!workspace || workspace_bytes < n_ws)) return CSP_ERR_WORKSPACE;
-        if ((uintptr_t)workspace & 7u) return CSP_ERR_WORKSPACE;
-        if ((uintptr_t)grad_coeffs & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // p_bar records are read as 2-element vectors
+        rc = check_device_args(s, n_ws, workspace, workspace_bytes, grad_coeffs);
+        if (rc != CSP_OK) return rc;
     } else if (!offsets_ok(desc, s)) {
         return CSP_ERR_INVALID_ARG;
     }
@@ -1771,9 +1776,8 @@ int csp_minsnap_solve_knots_batch(const csp_minsnap_desc *desc, const void *wayp
     if (!waypoints || !times || !knot_mask || !knot_values || !coeffs) return CSP_ERR_INVALID_ARG;
     const size_t n_ws = knots_ws_bytes(s);
     if (desc->mem_space == CSP_MEM_DEVICE) {
-        if (!workspace || workspace_bytes < n_ws) return CSP_ERR_WORKSPACE;
-        if ((uintptr_t)workspace & 7u) return CSP_ERR_WORKSPACE;
-        if ((uintptr_t)coeffs & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // records are stored as 2-element vectors
+        rc = check_device_args(s, n_ws, workspace, workspace_bytes, coeffs);
+        if (rc != CSP_OK) return rc;
     } else if (!offsets_ok(desc, s)) {
         return CSP_ERR_INVALID_ARG;
     }
@@ -1818,9 +1822,8 @@ int csp_minsnap_solve_knots_batch_vjp(const csp_minsnap_desc *desc, const void *
     if (!grad_waypoints && !grad_times && !grad_knot_values) return CSP_ERR_INVALID_ARG;
     const size_t n_ws = knots_vjp_ws_bytes(s, grad_coeffs != nullptr);
     if (desc->mem_space == CSP_MEM_DEVICE) {
-        if (!workspace || workspace_bytes < n_ws) return CSP_ERR_WORKSPACE;
-        if ((uintptr_t)workspace & 7u) return CSP_ERR_WORKSPACE;
-        if ((uintptr_t)grad_coeffs & (s.f32 ? 7u : 15u)) return CSP_ERR_INVALID_ARG;   // p_bar records are read as 2-element vectors
+        rc = check_device_args(s, n_ws, workspace, workspace_bytes, grad_coeffs);
+        if (rc != CSP_OK) return rc;
     } else if (!offsets_ok(desc, s)) {
         return CSP_ERR_INVALID_ARG;
     }

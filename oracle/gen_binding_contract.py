@@ -174,7 +174,34 @@ class NewStream:
     """stream=: a stream of the caller's (device table), any handle (host table, where it is ignored)."""
 
 
+class Np:
+    """An input that stays a numpy array in both tables (knots_from_bc's arrays beside device waypoints)."""
+    def __init__(self, a):
+        self.a = a
+
+
+class Backward:
+    """backward=: the case calls an *_autograd function, then backward() of the sum of the outputs in `loss` ("coeffs" or
+    "values": the first output, "cost": the second); of `inputs`, the function's differentiable ones, those in `wrt` require grad.
+    The row's result also holds the shape and dtype, or None, of every such input's .grad."""
+    def __init__(self, loss, inputs, wrt):
+        self.loss, self.inputs, self.wrt = loss, inputs, wrt
+
+
+def _forward_backward(target, kw, bw):
+    """What the function returned, and the (name, .grad) of every differentiable input after backward()."""
+    for n in bw.wrt:
+        kw[n].requires_grad_()
+    res = target(**kw)
+    outs = dict(zip(("coeffs", "cost"), res if isinstance(res, tuple) else (res,)))
+    outs["values"] = outs["coeffs"]   # eval_batch_autograd's one output
+    sum(outs[n].double().sum() for n in bw.loss).backward()
+    return res, [("grad " + n, getattr(kw[n], "grad", None)) for n in bw.inputs]
+
+
 def _materialise(v, space, keep):
+    if isinstance(v, Np):
+        return _materialise(v.a, "host", keep)
     if isinstance(v, (NC, Off)):
         a = _materialise(v.a, space, keep)
         if space == "host":
@@ -221,12 +248,15 @@ def run_case(csp, rec, space, fn, kwargs):
         if space == "host" and any(isinstance(v, CpuTorch) for v in kwargs.values()):
             return None
         raise
-    roles = {}
+    roles, grads, bw = {}, [], kw.pop("backward", None)
     for k, v in kw.items():
         _add_roles(roles, k, v)
     try:
         target = getattr(csp, fn)
-        res = target(**kw)
+        if bw is not None:
+            res, grads = _forward_backward(target, kw, bw)
+        else:
+            res = target(**kw)
         if isinstance(target, type):   # a Prepared* class: the construction, then one run()
             n_ctor = len(rec.calls)
             ret = res.run()
@@ -244,7 +274,7 @@ def run_case(csp, rec, space, fn, kwargs):
         attrs = _attributes(res)
     for n, v in attrs:
         _add_roles(roles, n, v)
-    row = {"calls": rec.resolve(roles), "result": {n: _describe(v) for n, v in attrs}}
+    row = {"calls": rec.resolve(roles), "result": {n: _describe(v) for n, v in attrs + grads}}   # a .grad names no pointer
     if isinstance(target, type):
         row["calls_in_constructor"] = n_ctor
     return row
@@ -451,6 +481,142 @@ def cases(space):
     add("base", "bezier_generate_batch", waypoints=bwp, offsets=boff, capacity=64)
     add("f32, non-contiguous, every parameter", "bezier_generate_batch", waypoints=NC(f4(bwp)), offsets=NC(boff.astype(np.int32)),
         resolution=0.5, min_radius=2.0, capacity=128)
+
+    # ---- reverse mode, knots and evaluation.  Appended here: every draw above keeps its place in the rng's sequence.
+    subsets = lambda names: [tuple(n for k, n in enumerate(names) if m >> k & 1) for m in range(1 << len(names))]
+    nB = lambda t: t.shape[0] if t.ndim == 2 else off.size - 1
+    gj = lambda w, t: dict(grad_cost=rng.normal(size=nB(t)))
+    wrong = np.zeros((3, 3, 3, 8))   # a grad_coeffs of the wrong size
+
+    # ---- solve_periodic_batch_vjp
+    fn = "solve_periodic_batch_vjp"
+    U, R, ONE = family(fn, *loops, bc=False, extra=gco, b0=not dev, full=False)
+    add("order 3", fn, **dict(U, grad_coeffs=U["grad_coeffs"][..., :6]), order=3)
+    add("grad_cost", fn, **U, **gj(wp, tm))
+    add("ragged, grad_cost as f32", fn, **R, grad_cost=f4(gj(rwp, rtm)["grad_cost"]))
+    for want in ((), ("times",), ["times", "waypoints"]):
+        add("want=%r" % (want,), fn, **U, want=want)
+    add("want= an unknown name", fn, **U, want=("bc",))
+    add("want_status", fn, **U, want_status=True)
+    add("grad_coeffs not 16-byte aligned", fn, **dict(U, grad_coeffs=Off(U["grad_coeffs"])))
+    add("grad_coeffs in the other dtype, non-contiguous", fn, **dict(U, grad_coeffs=NC(f4(U["grad_coeffs"]))))
+    add("grad_coeffs of the wrong size", fn, **dict(U, grad_coeffs=wrong))
+    add("grad_cost of the wrong size", fn, **U, grad_cost=np.zeros(2))
+    add("workspace too small", fn, **U, workspace=WS(16))
+    add("workspace large enough", fn, **U, workspace=WS(1 << 20))
+
+    # ---- solve_knots_batch: the standard problem's knots (knots_from_bc), then a free start and a pinned interior knot
+    knots_from_bc = importlib.import_module("cs-pathplan_amd").knots_from_bc
+
+    def knots(w, t, order=4):
+        if t.ndim == 2:
+            mk, kv = knots_from_bc({3: bc3, 1: bc1}.get(t.shape[0]), t.shape[1], order, batch=t.shape[0])
+        else:
+            mk, kv = (np.concatenate([a[0] for a in part])
+                      for part in zip(*(knots_from_bc(None, int(n), order) for n in np.diff(off))))
+        return dict(knot_mask=mk, knot_values=kv)
+
+    chains = tuple(dict(d, **knots(d["waypoints"], d["times"])) for d in base)
+    fn = "solve_knots_batch"
+    U, R, ONE = family(fn, *chains, bc=False, b0=not dev, full=False)
+    pinned = dict(U, knot_mask=U["knot_mask"].copy(), knot_values=U["knot_values"] + rng.normal(0, 0.3, size=(3, 5, 3, 3)))
+    pinned["knot_mask"][:, 0], pinned["knot_mask"][:, 2] = 0, 0b001
+    add("a free start, velocity pinned at knot 2", fn, **pinned)
+    add("order 3", fn, **dict(U, **knots(wp, tm, order=3)), order=3)
+    add("want_cost", fn, **U, want_cost=True)
+    add("knot_mask of the wrong size", fn, **dict(U, knot_mask=U["knot_mask"][:, :4]))
+    add("knot_values of the wrong size", fn, **dict(U, knot_values=U["knot_values"][:, :, :2]))
+    add("knot_mask and knot_values as numpy arrays", fn, **dict(U, knot_mask=Np(U["knot_mask"]), knot_values=Np(U["knot_values"])))
+    add("workspace too small", fn, **U, want_cost=True, workspace=WS(16))
+    add("workspace large enough", fn, **U, workspace=WS(1 << 20))
+
+    # ---- solve_knots_batch_vjp
+    fn = "solve_knots_batch_vjp"
+    U, R, ONE = family(fn, *chains, bc=False, extra=lambda w, t: dict(gco(w, t), **gj(w, t)), b0=not dev, full=False)
+    only = lambda d, drop: {k: v for k, v in d.items() if k != drop}
+    add("a free start, velocity pinned at knot 2", fn, **dict(U, knot_mask=pinned["knot_mask"], knot_values=pinned["knot_values"]))
+    add("order 3", fn, **dict(U, **knots(wp, tm, order=3), grad_coeffs=U["grad_coeffs"][..., :6]), order=3)
+    add("grad_coeffs alone", fn, **only(U, "grad_cost"))
+    add("grad_cost alone", fn, **only(U, "grad_coeffs"))
+    add("neither cotangent", fn, **only(only(U, "grad_cost"), "grad_coeffs"))
+    for want in subsets(("waypoints", "times", "knot_values")):
+        add("want=%r" % (want,), fn, **U, want=want)
+    add("want= a list", fn, **U, want=["knot_values", "waypoints"])
+    add("want= an unknown name", fn, **U, want=("bc",))
+    add("want_status", fn, **U, want_status=True)
+    add("knot_mask and knot_values as numpy arrays", fn, **dict(U, knot_mask=Np(U["knot_mask"]), knot_values=Np(U["knot_values"])))
+    add("grad_coeffs not 16-byte aligned", fn, **dict(U, grad_coeffs=Off(U["grad_coeffs"])))
+    add("grad_coeffs in the other dtype, non-contiguous", fn, **dict(U, grad_coeffs=NC(f4(U["grad_coeffs"]))))
+    add("grad_coeffs of the wrong size", fn, **dict(U, grad_coeffs=wrong))
+    add("grad_cost of the wrong size", fn, **dict(U, grad_cost=np.zeros(2)))
+    add("workspace too small", fn, **U, workspace=WS(16))
+    add("workspace large enough", fn, **U, workspace=WS(1 << 20))
+    add("grad_cost alone, workspace large enough", fn, **only(U, "grad_coeffs"), workspace=WS(1 << 20))
+
+    # ---- eval_batch, eval_batch_vjp (no _CallInputs: times / coeffs / query)
+    Q = 5
+    eco, eco1 = rng.normal(0, 0.5, size=(3, 4, 3, 8)), rng.normal(0, 0.5, size=(1, 4, 3, 8))
+    qry = lambda t: rng.uniform(0, 1, size=(t.shape[0], Q)) * t.sum(axis=1, keepdims=True)
+    rq = rng.uniform(0, 1, size=(3, Q)) * np.add.reduceat(rtm, off[:-1])[:, None]
+    EU, ER = dict(times=tm, coeffs=eco, query=qry(tm)), dict(times=rtm, coeffs=eco.reshape(-1, 3, 8)[:6], query=rq, seg_offsets=off)
+    EONE = dict(times=tm1, coeffs=eco1, query=qry(tm1))
+    gout = rng.normal(size=(3, Q, 3, 3))
+    for fn, g in (("eval_batch", {}), ("eval_batch_vjp", dict(grad_out=gout))):
+        add("uniform", fn, **EU, **g)
+        add("ragged", fn, **ER, **g)
+        add("ragged, max_segments given", fn, **ER, **g, max_segments=3)
+        add("B = 1", fn, **EONE, **{k: v[:1] for k, v in g.items()})
+        add("order given", fn, **EU, **g, order=4)
+        add("order 3", fn, **dict(EU, coeffs=eco[..., :6]), **g)
+        add("Q = 0", fn, **dict(EU, query=np.zeros((3, 0))), **{k: v[:, :0] for k, v in g.items()})
+        add("want_status", fn, **EU, **g, want_status=True)
+        add("non-contiguous inputs", fn, **{k: NC(v) for k, v in ER.items()}, **{k: NC(v) for k, v in g.items()})
+        add("f32 times, f64 coeffs and query", fn, **dict(EU, times=f4(tm)), **g)
+        add("stream", fn, **EU, **g, stream=NewStream())
+        add("coeffs not 16-byte aligned", fn, **dict(EU, coeffs=Off(eco)), **g)
+        add("coeffs of the wrong size", fn, **dict(EU, coeffs=eco[:, :3]), **g)
+        add("query [2,Q]", fn, **dict(EU, query=EU["query"][:2]), **g)
+        add("query [Q]", fn, **dict(EU, query=EU["query"][0]), **g)
+    add("want_seg_index", "eval_batch", **EU, want_seg_index=True)
+    add("num_derivs=1", "eval_batch", **EU, num_derivs=1)
+    fn = "eval_batch_vjp"
+    add("num_derivs given, grad_out [B,Q,9]", fn, **EU, grad_out=gout.reshape(3, Q, 9), num_derivs=3)
+    add("num_derivs taken from grad_out [B,Q,2,3]", fn, **EU, grad_out=gout[:, :, :2])
+    add("grad_out of the wrong size", fn, **EU, grad_out=gout[:, :, :2], num_derivs=3)
+    add("grad_out in the other dtype", fn, **EU, grad_out=f4(gout))
+    for want in subsets(("coeffs", "times", "query")):
+        add("want=%r" % (want,), fn, **EU, grad_out=gout, want=want)
+    add("want= a list", fn, **EU, grad_out=gout, want=["query", "coeffs"])
+    add("want= an unknown name", fn, **EU, grad_out=gout, want=("waypoints",))
+
+    # ---- the *_autograd functions: forward, then backward() (device memory only)
+    if dev:
+        def autograd(fn, inputs, losses, U, R, U3=None):
+            for loss, kw in losses:
+                for wrt in (inputs,) + tuple((n,) for n in inputs):
+                    add("loss on %s%s, grad of %s" % (" + ".join(loss), ", with_cost" if kw.get("with_cost") else "", ", ".join(wrt)),
+                        fn, **U, **kw, backward=Backward(loss, inputs, wrt))
+            add("ragged, loss on %s" % " + ".join(loss), fn, **R, **kw, backward=Backward(loss, inputs, inputs))
+            if U3 is not None:
+                add("order 3, f32, loss on %s" % " + ".join(loss), fn, **{k: f4(v) if v.dtype == np.float64 else v for k, v in U3.items()},
+                    order=3, **kw, backward=Backward(loss, inputs, inputs))
+
+        C = dict(with_cost=True)
+        losses = ((("coeffs",), {}), (("coeffs",), C), (("cost",), C), (("coeffs", "cost"), C))
+        U, R = dict(base[0], bc=bc3), dict(base[1], bc=bc3)
+        autograd("solve_batch_autograd", ("waypoints", "times", "bc"), losses, U, R, U)
+        add("bc [4,3], loss on coeffs + cost, grad of bc", "solve_batch_autograd", **base[0], bc=bc1[0], with_cost=True,
+            backward=Backward(("coeffs", "cost"), ("waypoints", "times", "bc"), ("bc",)))
+        add("bc=None, loss on cost, grad of times", "solve_batch_autograd", **base[0], with_cost=True,
+            backward=Backward(("cost",), ("waypoints", "times"), ("times",)))
+        autograd("solve_periodic_batch_autograd", ("waypoints", "times"), losses, loops[0], loops[1], loops[0])
+        U = chains[0]
+        autograd("solve_knots_batch_autograd", ("waypoints", "times", "knot_values"), losses, U, chains[1],
+                 dict(U, **knots(wp, tm, order=3)))
+        add("knot_mask and knot_values as numpy arrays, loss on cost", "solve_knots_batch_autograd",
+            **dict(U, knot_mask=Np(U["knot_mask"]), knot_values=Np(U["knot_values"])), with_cost=True,
+            backward=Backward(("cost",), ("waypoints", "times"), ("waypoints", "times")))
+        autograd("eval_batch_autograd", ("coeffs", "times", "query"), ((("values",), {}),), EU, ER)
     return [("%s: %s" % (fn, name), fn, kw) for name, fn, kw in out]
 
 
