@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = (
     "csp_minsnap_solve_periodic_batch_vjp", "csp_minsnap_periodic_vjp_workspace_bytes",
     "csp_minsnap_solve_knots_batch", "csp_minsnap_knots_workspace_bytes",
     "csp_minsnap_solve_knots_batch_vjp", "csp_minsnap_knots_vjp_workspace_bytes",
+    "csp_minsnap_optimize_times_knots_batch", "csp_minsnap_knots_timeopt_workspace_bytes",
     "csp_minsnap_eval_batch", "csp_minsnap_eval_batch_vjp",
     "csp_minsnap_solve_mixed", "csp_minsnap_mixed_workspace_bytes", "csp_minsnap_solve_multi",
     "csp_minsnap_plan_batch", "csp_minsnap_plan_workspace_bytes", "csp_minsnap_sample_batch",
@@ -143,6 +144,8 @@ _PROTOTYPES = {
     "csp_minsnap_knots_workspace_bytes": (_SZ, [_D]),
     "csp_minsnap_solve_knots_batch_vjp": (_I, [_D] + [_P] * 11 + [_SZ, _P]),
     "csp_minsnap_knots_vjp_workspace_bytes": (_SZ, [_D, _I]),
+    "csp_minsnap_optimize_times_knots_batch": (_I, [_D, ctypes.POINTER(TimeOptParams)] + [_P] * 10 + [_SZ, _P]),
+    "csp_minsnap_knots_timeopt_workspace_bytes": (_SZ, [_D]),
     "csp_minsnap_eval_batch": (_I, [_D, _P, _P, _P, _I64, _I32, _P, _P, _P, _P]),
     "csp_minsnap_eval_batch_vjp": (_I, [_D, _P, _P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
     "csp_minsnap_solve_multi": (_I, [_D, _I] + [_P] * 7),
@@ -847,6 +850,38 @@ def solve_knots_batch_vjp(waypoints, times, knot_mask, knot_values, grad_coeffs=
     _check(_lib.csp_minsnap_solve_knots_batch_vjp(ctypes.byref(desc), p(ci.waypoints), p(ci.times), p(mk), p(kv), p(gco), p(gj),
                                                   p(gwp), p(gtm), p(gkv), p(stt), wsp, need, mem.stream(stream)))
     return KnotsVjpResult(gwp, gtm, gkv, stt)
+
+
+def knots_timeopt_workspace_bytes(desc):
+    return int(_lib.csp_minsnap_knots_timeopt_workspace_bytes(ctypes.byref(desc)))
+
+
+def optimize_times_knots_batch(waypoints, times, knot_mask, knot_values, order=4, mode="fixed_total", time_weight=0.0,
+                               min_time=0.01, tol=1e-6, max_iters=100, want_coeffs=True, vel_zero_weight=0.0,
+                               seg_offsets=None, max_segments=None, vel_zero_weight_per_traj=None, workspace=None, stream=None):
+    """Segment times that minimise the snap cost under per-knot derivative constraints
+    (csp_minsnap_optimize_times_knots_batch): optimize_times_batch for the problem of solve_knots_batch, per
+    trajectory in one launch.  knot_mask / knot_values as in solve_knots_batch (knots_from_bc's numpy arrays may be passed
+    beside device waypoints); mode, time_weight, min_time, tol and max_iters as in optimize_times_batch.  Returns a
+    TimeOptResult; coeffs, when wanted, are solve_knots_batch's at the returned times (bit-equal).  A trajectory with fewer
+    constraints than `order` is returned unchanged with status TRAJ_NOT_SPD, iterations 0 and NaN objectives."""
+    if mode not in _TIMEOPT_MODES:
+        raise ValueError("mode: one of %r" % (tuple(_TIMEOPT_MODES),))
+    ci = _CallInputs(waypoints, times, None, seg_offsets, max_segments, vel_zero_weight_per_traj)
+    mem, p = ci.mem, ci.mem.ptr
+    mk, kv = _knot_arrays(ci, knot_mask, knot_values, order)
+    desc = ci.desc(order, False, 0.0, vel_zero_weight)
+    prm = make_timeopt_params(_TIMEOPT_MODES[mode], time_weight, min_time, tol, max_iters)
+    tout = mem.empty(ci.times.shape, ci.io)
+    co = mem.empty(ci.coeffs_shape(order), ci.io) if want_coeffs else None
+    obj = mem.empty((ci.B, 2), "f64")
+    its = mem.empty((ci.B,), "i32")
+    stt = mem.empty((ci.B,), "i32")
+    wsp, need = mem.workspace(knots_timeopt_workspace_bytes(desc), workspace)
+    _check(_lib.csp_minsnap_optimize_times_knots_batch(ctypes.byref(desc), ctypes.byref(prm), p(ci.waypoints), p(ci.times),
+                                                       p(mk), p(kv), p(tout), p(co), p(obj), p(its), p(stt), wsp, need,
+                                                       mem.stream(stream)))
+    return TimeOptResult(tout, co, obj, its, stt)
 
 
 def _knots_forward(wp, tm, kv, knot_mask, with_cost, kw):

@@ -18,6 +18,7 @@
 // pass after every acceptance.
 #include "minsnap_device.h"
 #include "minsnap_launch.h"
+#include "minsnap_spg.h"
 
 namespace csp {
 
@@ -203,30 +204,6 @@ __device__ __forceinline__ void load_bc(const TimeOptArgs &a, int64_t b, double 
         }
 }
 
-// Euclidean projection onto {sum_j y_j = C, y_j >= lo} (fixed_total) or {y_j >= lo} (clip): y_j = max(v_j - theta, lo).
-// theta by Michelot's algorithm, written over theta alone: the active set {v_j - theta > lo} only shrinks while theta
-// grows, so a pass whose count does not change ends it (at most S + 1 passes).  v(j) is recomputed per pass.
-template <typename F>
-__device__ double proj_theta(F v, int S, bool fixed_total, double C, double lo) {
-    if (!fixed_total) return 0.0;
-    double sum = 0.0;
-    for (int j = 0; j < S; ++j) sum += v(j);
-    double theta = (sum - C) / double(S);
-    int n = S;
-    for (int pass = 0; pass <= S; ++pass) {
-        double s = 0.0;
-        int m = 0;
-        for (int j = 0; j < S; ++j) {
-            const double vj = v(j);
-            if (vj - theta > lo) { s += vj; ++m; }
-        }
-        if (m == n || m == 0) break;
-        n = m;
-        theta = (s - C + double(S - n) * lo) / double(n);
-    }
-    return theta;
-}
-
 }  // namespace
 
 // csp_minsnap_cost_batch: J and (optionally) dJ/dT at the given times, one lane per trajectory.
@@ -251,11 +228,8 @@ __global__ void __launch_bounds__(64) minsnap_cost_kernel(TimeOptArgs a) {
     if (a.status) a.status[b] = status;
 }
 
-// csp_minsnap_optimize_times_batch: spectral projected gradient (Barzilai-Borwein step, monotone Armijo backtracking with
-// a safeguarded quadratic step) in the scaled variables x = T / tau (tau = the start's mean time) and f / f0.  In T the
-// step is  T - tau * alpha * g^,  g^ = (tau / f0) grad f,  and the projection onto the scaled set is the projection onto
-// {sum T = C, T >= t_min} scaled by tau, so everything is done in T with exact bounds.  One evaluation site: every pass
-// of the loop evaluates the buffer `eb` (the start, then trial points) and then decides what to do next.
+// csp_minsnap_optimize_times_batch: the spectral projected gradient loop of minsnap_spg.h (shared with the optimiser under
+// per-knot constraints, minsnap_knots_timeopt.hip) over cost_pass.
 template <int O, typename IO>
 __global__ void __launch_bounds__(64) minsnap_timeopt_kernel(TimeOptArgs a) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -272,155 +246,30 @@ __global__ void __launch_bounds__(64) minsnap_timeopt_kernel(TimeOptArgs a) {
     double *Gb[2] = {a.vec + 2 * plane + b, a.vec + 3 * plane + b};   // dJ/dT at those times
     const bool ft = a.mode == CSP_TIMEOPT_FIXED_TOTAL_V;
     const double lo = a.min_time, rho = ft ? 0.0 : a.time_weight;
-    constexpr double kArmijo = 1e-4, kAlphaMin = 1e-10, kAlphaMax = 1e4;
-    constexpr int kMaxBacktrack = 30;
 
     int status = 0, iters = 0;
     double f0 = 0.0, f = 0.0;
     if (S >= 1) {
-        // start: the input's projection (the input itself when it is feasible)
-        double C = 0.0;
-        bool feasible = true;
-        for (int j = 0; j < S; ++j) {
-            const double t = double(tin[j]);
-            C += t;
-            feasible = feasible && t >= lo;
-        }
-        // an inf / NaN time: the total has no projection (Michelot's theta would be NaN and every entry would come
-        // back as min_time), and there is no start to evaluate
-        const bool nonfinite = !(fabs(C) <= 1.7976931348623157e308);
-        if (nonfinite || (ft && C < double(S) * lo)) {
-            // an infeasible fixed total -- device memory: the C-ABI could not check it on the host -- is reported not
-            // converged.  Either way the times are left as they came and nothing was evaluated.
+        double C;
+        const int stop = spg_start<IO>(tin, S, ft, lo, Tb[0], B, C);
+        if (stop) {
+            // the times are left as they came and nothing was evaluated
             for (int j = 0; j < S; ++j) tout[j] = tin[j];
             if (a.objective) { a.objective[2 * b] = __builtin_nan(""); a.objective[2 * b + 1] = __builtin_nan(""); }
             if (a.iterations) a.iterations[b] = 0;
-            if (a.status) a.status[b] = nonfinite ? CSP_TRAJ_NONFINITE_BIT : CSP_TRAJ_NOT_CONVERGED_BIT;
+            if (a.status) a.status[b] = stop;
             return;
-        }
-        const double th0 = feasible ? 0.0 : proj_theta([&](int j) { return double(tin[j]); }, S, ft, C, lo);
-        for (int j = 0; j < S; ++j) {
-            const double t = double(tin[j]);
-            Tb[0][(int64_t)j * B] = feasible ? t : fmax(t - th0, lo);
         }
         double x0[O - 1][3], xS[O - 1][3];
         load_bc<O, IO>(a, b, x0, xS);
         const double vw = a.vw_per ? a.vw_per[b] : a.vel_zero_weight;
         const IO *wp = (const IO *)a.wp + (seg0 + b) * 3;
         double *ws = (double *)a.ws + b;
-
-        int cur = 0;                 // buffer of the accepted iterate
-        bool first = true, active = status == 0;
-        double tau = 1.0, k = 1.0, alpha = 1.0, lam = 1.0, thd = 0.0, gd = 0.0, fs = 1.0;
-        // tau * alpha * g^_j = step * grad f_j
-        auto pg_measure = [&](int c) {   // max_j |T_j - P(T_j - tau g^_j)| / tau
-            const double st = tau * k;
-            const double th = proj_theta([&](int j) { return Tb[c][(int64_t)j * B] - st * (Gb[c][(int64_t)j * B] + rho); },
-                                         S, ft, C, lo);
-            double m = 0.0;
-            for (int j = 0; j < S; ++j) {
-                const double t = Tb[c][(int64_t)j * B];
-                m = fmax(m, fabs(t - fmax(t - st * (Gb[c][(int64_t)j * B] + rho) - th, lo)));
-            }
-            return m / tau;
-        };
-        // direction d = P(T - tau alpha g^) - T (its theta kept in thd), gd = grad f . d; then the trial T + lam d
-        auto direction = [&]() {
-            const double st = tau * alpha * k;
-            thd = proj_theta([&](int j) { return Tb[cur][(int64_t)j * B] - st * (Gb[cur][(int64_t)j * B] + rho); }, S, ft, C, lo);
-            gd = 0.0;
-            for (int j = 0; j < S; ++j) {
-                const double t = Tb[cur][(int64_t)j * B], gj = Gb[cur][(int64_t)j * B] + rho;
-                gd = fma_<double>(gj, fmax(t - st * gj - thd, lo) - t, gd);
-            }
-        };
-        auto trial = [&]() {
-            const double st = tau * alpha * k;
-            double *tt = Tb[cur ^ 1];
-            for (int j = 0; j < S; ++j) {
-                const double t = Tb[cur][(int64_t)j * B], gj = Gb[cur][(int64_t)j * B] + rho;
-                tt[(int64_t)j * B] = fma_<double>(lam, fmax(t - st * gj - thd, lo) - t, t);
-            }
-            // T + lam d is feasible in exact arithmetic; the projection removes the rounding (sum drift, bounds)
-            const double th = proj_theta([&](int j) { return tt[(int64_t)j * B]; }, S, ft, C, lo);
-            for (int j = 0; j < S; ++j) tt[(int64_t)j * B] = fmax(tt[(int64_t)j * B] - th, lo);
-        };
-
-        int eb = 0, backtracks = 0;
-        while (active) {
-            double J = 0.0;
-            const int st = cost_pass<O, IO, double, double>(wp, Tb[eb], B, x0, xS, vw, ws, B, S, Gb[eb], B, J);
-            double sumT = 0.0;
-            if (rho != 0.0)
-                for (int j = 0; j < S; ++j) sumT += Tb[eb][(int64_t)j * B];
-            const double fe = fma_<double>(rho, sumT, J);
-            if (st) {
-                if (first) {   // the start itself: the trajectory stops there
-                    status |= st;
-                    f0 = f = fe;
-                    break;
-                }
-                // a trial point the solve cannot take (extreme times after a long step): rejected like a failed
-                // Armijo test, with a tenth of the step
-                if (++backtracks > kMaxBacktrack) {
-                    status |= CSP_TRAJ_NOT_CONVERGED_BIT;
-                    break;
-                }
-                lam *= 0.1;
-                trial();
-                continue;
-            }
-            bool accept;
-            if (first) {
-                first = false;
-                accept = false;
-                f0 = f = fe;
-                fs = f0 > 0.0 ? f0 : 1.0;
-                tau = 0.0;
-                for (int j = 0; j < S; ++j) tau += Tb[0][(int64_t)j * B];
-                tau /= double(S);
-                k = tau / fs;
-                const double pg = pg_measure(cur);
-                if (pg <= a.tol || iters >= a.max_iters) { if (pg > a.tol) status |= CSP_TRAJ_NOT_CONVERGED_BIT; break; }
-                alpha = fmin(kAlphaMax, fmax(kAlphaMin, 1.0 / pg));
-            } else {
-                accept = fe <= f && fe <= fma_<double>(kArmijo * lam, gd, f);
-                if (!accept) {   // backtrack: minimiser of the quadratic through f, gd and fe, kept in [0.1, 0.5] lam
-                    if (++backtracks > kMaxBacktrack) {
-                        status |= CSP_TRAJ_NOT_CONVERGED_BIT;   // no decrease within rounding: stop at the accepted point
-                        break;
-                    }
-                    const double lt = -0.5 * lam * lam * gd / (fe - f - lam * gd);
-                    lam = (lt >= 0.1 * lam && lt <= 0.5 * lam) ? lt : 0.5 * lam;
-                    trial();
-                    continue;
-                }
-            }
-            if (accept) {
-                // Barzilai-Borwein step from s = (T+ - T) / tau and y = g^+ - g^
-                const int nx = cur ^ 1;
-                double ss = 0.0, sy = 0.0;
-                for (int j = 0; j < S; ++j) {
-                    const double s = (Tb[nx][(int64_t)j * B] - Tb[cur][(int64_t)j * B]) / tau;
-                    ss = fma_<double>(s, s, ss);
-                    sy = fma_<double>(s, k * (Gb[nx][(int64_t)j * B] - Gb[cur][(int64_t)j * B]), sy);
-                }
-                cur = nx;
-                f = fe;
-                ++iters;
-                const double pg = pg_measure(cur);
-                // no positive curvature along s: the start's rule, a step of unit length in the scaled variables
-                alpha = fmin(kAlphaMax, fmax(kAlphaMin, sy > 0.0 ? ss / sy : 1.0 / pg));
-                if (pg <= a.tol) break;
-                if (iters >= a.max_iters) { status |= CSP_TRAJ_NOT_CONVERGED_BIT; break; }
-            }
-            direction();
-            lam = 1.0;
-            backtracks = 0;
-            trial();
-            eb = cur ^ 1;
-        }
-        for (int j = 0; j < S; ++j) tout[j] = IO(Tb[cur][(int64_t)j * B]);
+        const SpgResult r = spg_minimise(
+            [&](int eb, double &J) { return cost_pass<O, IO, double, double>(wp, Tb[eb], B, x0, xS, vw, ws, B, S, Gb[eb], B, J); },
+            Tb, Gb, B, S, ft, C, lo, rho, a.tol, a.max_iters);
+        status = r.status; iters = r.iters; f0 = r.f0; f = r.f;
+        for (int j = 0; j < S; ++j) tout[j] = IO(Tb[r.cur][(int64_t)j * B]);
     }
     if (a.objective) { a.objective[2 * b] = f0; a.objective[2 * b + 1] = f; }
     if (a.iterations) a.iterations[b] = iters;
