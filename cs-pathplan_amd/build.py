@@ -18,9 +18,9 @@ HEAVY = ["minsnap_fixed_o4b.hip", "minsnap_fixed_o4c.hip", "minsnap_fixed_o4a.hi
          "minsnap_fixedpath_o4b.hip", "minsnap_fixedpath_o4c.hip", "minsnap_fixedpath_o4a.hip",
          "minsnap_fixedpath_o3b.hip", "minsnap_fixedpath_o3.hip", "minsnap_fixedpath_o2.hip",
          "minsnap_fixed_o3.hip", "minsnap_fixed_o2.hip", "minsnap_fixed_o5.hip"]
-SOURCES = HEAVY + ["minsnap_capi.hip", "minsnap_generic.hip", "minsnap_vjp.hip", "minsnap_timeopt.hip", "minsnap_periodic.hip", "minsnap_periodic_vjp.hip", "minsnap_knots.hip", "minsnap_knots_vjp.hip", "minsnap_knots_timeopt.hip", "minsnap_eval.hip", "minsnap_chunked.hip", "minsnap_mixed.hip", "minsnap_twist.hip", "minsnap_twist_f32.hip", "minsnap_twist_f32s.hip", "minsnap_twist_f64.hip", "minsnap_twist_f64s.hip", "minsnap_span.hip", "minsnap_fixed.hip",
+SOURCES = HEAVY + ["minsnap_capi.hip", "minsnap_generic.hip", "minsnap_vjp.hip", "minsnap_timeopt.hip", "minsnap_periodic.hip", "minsnap_periodic_vjp.hip", "minsnap_knots.hip", "minsnap_knots_vjp.hip", "minsnap_knots_timeopt.hip", "minsnap_periodic_timeopt.hip", "minsnap_eval.hip", "minsnap_chunked.hip", "minsnap_mixed.hip", "minsnap_twist.hip", "minsnap_twist_f32.hip", "minsnap_twist_f32s.hip", "minsnap_twist_f64.hip", "minsnap_twist_f64s.hip", "minsnap_span.hip", "minsnap_fixed.hip",
                    "minsnap_timealloc.hip", "minsnap_plan.hip", "geo.hip", "alt.hip", "bezier.hip"]
-HEADERS = ["minsnap_device.h", "minsnap_launch.h", "minsnap_vjp.h", "minsnap_vjp_device.h", "minsnap_periodic_vjp.h", "minsnap_knots.h", "minsnap_knots_vjp.h", "minsnap_knots_timeopt.h", "minsnap_spg.h", "minsnap_eval.h", "minsnap_eval_plan.h", "minsnap_hoststage.h", "minsnap_timealloc.h", "minsnap_tables.h", "minsnap_fixed_plan.h", "minsnap_fixed_impl.h", "minsnap_fixed_path_impl.h", "minsnap_iface.h", "minsnap_chunked_impl.h", "minsnap_mixed.h", "minsnap_twist_impl.h", "minsnap_twist_launch.h", "minsnap_shard_schedule.h", "alt_cr_layout.h",
+HEADERS = ["minsnap_device.h", "minsnap_launch.h", "minsnap_vjp.h", "minsnap_vjp_device.h", "minsnap_periodic_vjp.h", "minsnap_knots.h", "minsnap_knots_vjp.h", "minsnap_knots_timeopt.h", "minsnap_periodic_timeopt.h", "minsnap_spg.h", "minsnap_eval.h", "minsnap_eval_plan.h", "minsnap_hoststage.h", "minsnap_timealloc.h", "minsnap_tables.h", "minsnap_fixed_plan.h", "minsnap_fixed_impl.h", "minsnap_fixed_path_impl.h", "minsnap_iface.h", "minsnap_chunked_impl.h", "minsnap_mixed.h", "minsnap_twist_impl.h", "minsnap_twist_launch.h", "minsnap_shard_schedule.h", "alt_cr_layout.h",
            os.path.join("..", "..", "include", "csp_minsnap.h"), os.path.join("..", "..", "include", "csp_geo.h"), os.path.join("..", "..", "include", "csp_alt.h"), os.path.join("..", "..", "include", "csp_bezier.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]

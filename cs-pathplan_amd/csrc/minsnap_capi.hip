@@ -12,6 +12,7 @@
 #include "minsnap_knots.h"
 #include "minsnap_knots_vjp.h"
 #include "minsnap_knots_timeopt.h"
+#include "minsnap_periodic_timeopt.h"
 #include "minsnap_vjp.h"
 #include "minsnap_hoststage.h"
 #include "minsnap_timealloc.h"
@@ -789,6 +790,45 @@ int dispatch_knots_timeopt(const csp_minsnap_desc *d, const csp_minsnap_timeopt_
     // the coefficients are csp_minsnap_solve_knots_batch's at the optimised times, in the factor region; the status stays
     // the optimiser's
     return dispatch_knots(d, s, wp, tout, mask, values, co, nullptr, nullptr, seg_off, vw_per, ws, st);
+}
+
+// csp_minsnap_optimize_times_periodic_batch: the periodic solve's scope and layouts, the time optimiser's parameters.  The
+// periodic solve's factor region (knots 1..Smax-1 of every loop), then the optimiser's four [Smax][B] vectors.
+size_t periodic_timeopt_ws_bytes(const Shape &s, size_t *vec_off) {
+    const size_t factors = periodic_ws_bytes(s);
+    if (vec_off) *vec_off = factors;
+    return factors + 4 * (size_t)s.Smax * (size_t)s.B * 8;
+}
+
+// offsets_checked: the host has seen the ragged offsets (CSP_MEM_HOST) and every S_b is within 0..Smax
+int dispatch_periodic_timeopt(const csp_minsnap_desc *d, const csp_minsnap_timeopt_params *p, const Shape &s, const void *wp,
+                              const void *tm, void *tout, void *co, double *obj, int32_t *iters, int32_t *status,
+                              const int64_t *seg_off, const double *vw_per, void *ws, bool offsets_checked, hipStream_t st) {
+    size_t vec_off = 0;
+    (void)periodic_timeopt_ws_bytes(s, &vec_off);
+    csp::PeriodicTimeOptArgs a{};
+    a.wp = wp; a.times = tm; a.times_out = tout; a.objective = obj; a.iterations = iters; a.status = status;
+    a.seg_off = s.ragged ? seg_off : nullptr;
+    a.ws = ws; a.vec = (double *)((char *)ws + vec_off); a.vw_per = vw_per;
+    a.vel_zero_weight = d->vel_zero_weight;
+    a.time_weight = p->time_weight; a.min_time = p->min_time; a.tol = p->tol; a.max_iters = p->max_iters;
+    a.B = s.B; a.S = s.S; a.Smax = s.Smax; a.order = s.order;
+    a.mode = p->mode == CSP_TIMEOPT_FIXED_TOTAL ? csp::CSP_TIMEOPT_FIXED_TOTAL_V : csp::CSP_TIMEOPT_TIME_PENALTY_V;
+    hipError_t e = csp::launch_periodic_timeopt(a, s.f32, st);
+    if (e != hipSuccess) return hip_fail(e, "periodic time optimiser launch");
+    if (!co) return CSP_OK;
+    // The coefficients are csp_minsnap_solve_periodic_batch's at the optimised times, in the factor region; the status
+    // stays the optimiser's.  That kernel has no length guard, so a ragged device batch (offsets the host cannot read)
+    // is launched over the table of launch_periodic_coeff_offsets, built in the optimiser's vectors, which are dead by
+    // now ((B + 1) * 8 <= 4 * Smax * B * 8 bytes): it is seg_off itself unless a trajectory is longer than Smax.
+    const int64_t *co_off = seg_off;
+    if (s.ragged && !offsets_checked) {
+        int64_t *table = (int64_t *)((char *)ws + vec_off);
+        e = csp::launch_periodic_coeff_offsets(seg_off, table, s.B, s.Smax, st);
+        if (e != hipSuccess) return hip_fail(e, "periodic coefficient offsets launch");
+        co_off = table;
+    }
+    return dispatch_periodic(d, s, wp, tout, co, nullptr, nullptr, nullptr, co_off, vw_per, ws, st);
 }
 
 }  // namespace
@@ -1925,6 +1965,49 @@ int csp_minsnap_optimize_times_knots_batch(const csp_minsnap_desc *desc, const c
         return dispatch_knots_timeopt(desc, prm, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr<const uint8_t>(o_mk), g.ptr(o_kv), g.ptr(o_to),
                                       g.ptr(o_co), g.ptr<double>(o_ob), g.ptr<int32_t>(o_it), g.ptr<int32_t>(o_st),
                                       g.ptr<const int64_t>(g.seg_off), g.ptr<const double>(g.vw_per), g.ptr(o_ws), st);
+    });
+}
+
+size_t csp_minsnap_periodic_timeopt_workspace_bytes(const csp_minsnap_desc *desc) {
+    Shape s;
+    if (validate_vjp(desc, s) != CSP_OK) return 0;
+    return periodic_timeopt_ws_bytes(s, nullptr);
+}
+
+int csp_minsnap_optimize_times_periodic_batch(const csp_minsnap_desc *desc, const csp_minsnap_timeopt_params *prm,
+                                              const void *waypoints, const void *times_in, void *times_out, void *coeffs,
+                                              double *objective, int32_t *iterations, int32_t *status, void *workspace,
+                                              size_t workspace_bytes, void *hip_stream) {
+    Shape s;
+    int rc = validate_timeopt(desc, prm, s);
+    if (rc != CSP_OK) return rc;
+    if (s.B == 0) return CSP_OK;
+    if (!waypoints || !times_in || !times_out) return CSP_ERR_INVALID_ARG;
+    const size_t n_ws = periodic_timeopt_ws_bytes(s, nullptr);
+    if (desc->mem_space == CSP_MEM_DEVICE) {
+        rc = check_device_args(s, n_ws, workspace, workspace_bytes, coeffs);
+        if (rc != CSP_OK) return rc;
+    } else {   // the caller's arrays can be read here
+        if (!offsets_ok(desc, s)) return CSP_ERR_INVALID_ARG;
+        if (prm->mode == CSP_TIMEOPT_FIXED_TOTAL && !totals_feasible(s, desc->seg_offsets, times_in, prm->min_time))
+            return CSP_ERR_INVALID_ARG;
+    }
+    rc = select_device(desc->device_id);
+    if (rc != CSP_OK) return rc;
+    hipStream_t st = (hipStream_t)hip_stream;
+
+    if (desc->mem_space == CSP_MEM_DEVICE)
+        return dispatch_periodic_timeopt(desc, prm, s, waypoints, times_in, times_out, coeffs, objective, iterations, status,
+                                         desc->seg_offsets, desc->vel_zero_weight_per_traj, workspace, false, st);
+
+    // CSP_MEM_HOST: as csp_minsnap_solve_periodic_batch
+    Stage g(desc, s, st, waypoints, times_in, nullptr);
+    const size_t o_to = g.out(times_out, g.z.tm), o_co = g.out(coeffs, g.z.co), o_ob = g.out(objective, (size_t)s.B * 16);
+    const size_t o_it = g.out(iterations, (size_t)s.B * 4), o_st = g.out(status, (size_t)s.B * 4), o_ws = g.hc.scratch(n_ws);
+    return g.run([&] {
+        return dispatch_periodic_timeopt(desc, prm, s, g.ptr(g.wp), g.ptr(g.tm), g.ptr(o_to), g.ptr(o_co), g.ptr<double>(o_ob),
+                                         g.ptr<int32_t>(o_it), g.ptr<int32_t>(o_st), g.ptr<const int64_t>(g.seg_off),
+                                         g.ptr<const double>(g.vw_per), g.ptr(o_ws), true, st);
     });
 }
 

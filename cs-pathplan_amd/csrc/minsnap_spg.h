@@ -1,6 +1,7 @@
 // minsnap_spg.h -- the per-lane spectral projected gradient loop of the segment-time optimisers, written
 // once over the "pass" that evaluates the cost and its time gradient: minsnap_timeopt.hip instantiates it with cost_pass
-// (the standard partition), minsnap_knots_timeopt.hip with the masked pass (per-knot derivative constraints, §23).
+// (the standard partition), minsnap_knots_timeopt.hip with the masked pass (per-knot derivative constraints, §23),
+// minsnap_periodic_timeopt.hip with the periodic pass (closed loops, §24).
 //
 // The iterate and the trial point live in the workspace, [buffer][segment][trajectory]: Tb[c][j * B] is time j of buffer
 // c, Gb[c][j * B] the cost's gradient there.  Everything is done in T with exact bounds; the scaled variables

@@ -104,7 +104,7 @@ enum { CSP_MEM_HOST = 0, CSP_MEM_DEVICE = 1 };
 #define CSP_TRAJ_SKIPPED 4     /* csp_minsnap_solve_mixed (and a device-memory csp_minsnap_eval_batch[_vjp] given a ragged length outside
                                   0..max_segments): the trajectory was NOT solved (its order is outside 2..5
                                   or its segment count outside 1..min(256, max_segments)); its coefficient block is left untouched (zero-filled with CSP_MEM_HOST) */
-#define CSP_TRAJ_NOT_CONVERGED 8 /* csp_minsnap_optimize_times[_knots]_batch only: the stopping rule was not met (max_iters reached, or
+#define CSP_TRAJ_NOT_CONVERGED 8 /* csp_minsnap_optimize_times[_knots|_periodic]_batch only: the stopping rule was not met (max_iters reached, or
                                   no decrease within rounding); the times returned are the last accepted ones          */
 
 typedef struct csp_minsnap_desc {
@@ -489,6 +489,69 @@ int csp_minsnap_optimize_times_knots_batch(const csp_minsnap_desc *desc, const c
 /* Device scratch bytes csp_minsnap_optimize_times_knots_batch needs (formula above; 0 for an invalid or unsupported
  * descriptor). */
 size_t csp_minsnap_knots_timeopt_workspace_bytes(const csp_minsnap_desc *desc);
+
+/* Lap-time optimisation of the PERIODIC (closed-loop) solve: csp_minsnap_optimize_times_batch for the
+ * problem of csp_minsnap_solve_periodic_batch.  Per loop, the segment times that minimise the snap cost J of the closed
+ * spline (fixed total: the lap time is kept) or J + rho sum T (time penalty), starting from times_in, in ONE launch: the
+ * same spectral projected gradient loop, constants, scaling, projection and stopping rule as
+ * csp_minsnap_optimize_times_batch (one copy of the loop serves all three kernels), every evaluation a bordered
+ * block-LDL^T sweep around the loop with the cost and its envelope-theorem time gradient from the back substitution.
+ * No atomics, every output written once by its owner: two calls give identical bits.
+ *   desc        : the scope, layouts (RAGGED LAYOUT: trajectory b owns waypoints AND times seg_offsets[b] ..
+ *                 seg_offsets[b+1]-1, no +b offset) and CSP_ERR_UNSUPPORTED cases of csp_minsnap_solve_periodic_batch
+ *                 (order 1 or 6+, path_weight != 0, CSP_FLAG_SEGMENT_MAJOR, CSP_FLAG_F32_ARITH); bc_per_trajectory is
+ *                 ignored; vel_zero_weight is honoured, scalar or per trajectory
+ *   prm         : the rules of csp_minsnap_optimize_times_batch: CSP_ERR_INVALID_ARG for NULL, a bad abi_version or
+ *                 mode, time_weight <= 0 with the time penalty, min_time <= 0, tol < 0, max_iters < 0, and (CSP_MEM_HOST)
+ *                 sum_j T_j^in < S * min_time with the fixed total.  With CSP_MEM_DEVICE the last check is per trajectory
+ *                 on the device: such a trajectory is returned unchanged with CSP_TRAJ_NOT_CONVERGED, iterations 0 and
+ *                 NaN objectives.
+ *   waypoints   : [B][S][3], the S distinct loop points (no repeated closing point)
+ *   times_in    : [B][S]; an entry below min_time is not an error, the start is the projection
+ *   times_out   : out, the layout of times_in
+ *   coeffs      : optional out, csp_minsnap_solve_periodic_batch(times_out) -- launched by that entry's own dispatch, so
+ *                 bit-equal to a separate call; 16-byte aligned (fp64) / 8-byte (fp32) for a device call
+ *   objective   : optional out, [B][2] f64: initial (at the start) and final objective (J, plus rho sum T)
+ *   iterations  : optional out, [B] i32 accepted iterations
+ *   status      : optional out, [B] i32.  Per trajectory, in this order:
+ *                 - S_b = 0 (ragged): status 0, objectives 0, iterations 0; nothing else is written for it.
+ *                 - a ragged trajectory longer than max_segments (CSP_MEM_DEVICE; CSP_MEM_HOST: CSP_ERR_INVALID_ARG):
+ *                   CSP_TRAJ_SKIPPED, times_out = times_in, NaN objectives, iterations 0; coeffs are not written.  The
+ *                   periodic solve has no length guard of its own and a table of offsets cannot leave one trajectory
+ *                   out, so the coefficient launch of such a batch writes NO trajectory's coefficients: the descriptor
+ *                   was wrong for the batch, every other output of every other trajectory is as without it.
+ *                 - an inf / NaN time: CSP_TRAJ_NONFINITE, the trajectory is returned unchanged (iterations 0, NaN
+ *                   objectives).
+ *                 - an infeasible fixed total (CSP_MEM_DEVICE): CSP_TRAJ_NOT_CONVERGED, returned unchanged, NaN
+ *                   objectives, iterations 0.
+ *                 - a solve that fails at the start (CSP_TRAJ_NOT_SPD / CSP_TRAJ_NONFINITE, e.g. an inf / NaN waypoint):
+ *                   the trajectory stops there, times_out = the start, iterations 0.  CSP_TRAJ_NOT_SPD: a pivot <= 0,
+ *                   the border's Schur complement included, or a time that is not > 0; CSP_TRAJ_NONFINITE: J or a
+ *                   gradient is inf/NaN.
+ *                 - CSP_TRAJ_NOT_CONVERGED after max_iters accepted iterations (max_iters = 0 returns the start) or 30
+ *                   backtracks without a decrease.
+ *                 - S = 1 with the fixed total has nothing to optimise: times_out = times_in bit for bit, final
+ *                   objective = initial objective (J = 0 for one knot, whatever w), iterations 0.  S = 1 with the time
+ *                   penalty is a real problem: J = 0 for every T, so the time runs to min_time (a converged trajectory
+ *                   that moved returns min_time itself, final objective time_weight * min_time).
+ *                 A bad trajectory does not change any output of another one.
+ *   workspace   : device scratch of csp_minsnap_periodic_timeopt_workspace_bytes(desc) bytes (CSP_MEM_DEVICE, 8-byte
+ *                 aligned); may be NULL/0 with CSP_MEM_HOST.  With o = order, Smax = num_segments (uniform) or
+ *                 max_segments (ragged):
+ *                   round_up_256((Smax - 1) * (2(o-1)^2 + 3(o-1)) * B * 8) + 4 * Smax * B * 8
+ *                 (the periodic solve's factor region, reused by the coefficient launch, then the optimiser's four
+ *                 vectors).  No slot is read before the same launch wrote it: stale contents change no output.
+ * Arguments (NULL prm / waypoints / times_in / times_out, the parameter rules, workspace size and alignment and the
+ * alignment of coeffs of a device call, ragged host offsets outside 0..max_segments, an infeasible host fixed total) are
+ * checked before a device is looked for.
+ * CSP_MEM_HOST: staged through the cached arena, synchronous.  CSP_MEM_DEVICE: asynchronous on `hip_stream`. */
+int csp_minsnap_optimize_times_periodic_batch(const csp_minsnap_desc *desc, const csp_minsnap_timeopt_params *prm,
+                                              const void *waypoints, const void *times_in, void *times_out, void *coeffs,
+                                              double *objective, int32_t *iterations, int32_t *status, void *workspace,
+                                              size_t workspace_bytes, void *hip_stream);
+/* Device scratch bytes csp_minsnap_optimize_times_periodic_batch needs (formula above; 0 for an invalid or unsupported
+ * descriptor, and for B = 0). */
+size_t csp_minsnap_periodic_timeopt_workspace_bytes(const csp_minsnap_desc *desc);
 
 /* The same solve spread over `ngpu` devices of this node from ONE process (the reference planner
  * is a single C++ process).  Trajectories are independent
